@@ -1,8 +1,17 @@
 """Train-step clips/s of the audio-visual hard-way step (BASELINE.json metric) on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--workload 1frame|tube|twoview]
-                    [--no-cpu-baseline]
+                    [--dump-outputs DIR] [--full [--no-cpu-baseline] [--no-peaks] [--traffic live|file|off]]
     (N>1: python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N)
+
+A plain run sets up, warms up (the first warm-up step is eager, then the step is captured), times K steps
+and prints the headline line: metric, value, unit, higher_is_better, dtype, ms_per_step (milliseconds per
+timed step), the configuration and the loss.  --dump-outputs DIR then writes what the last timed step left
+its caller as DIR/<name>.npy (float32): `loss` (the tensor step() returns), and fixed seeded samples
+(`sample_index` holds the positions) of `grad`, the flat gradient the step reduced, and `params`, the flat
+parameters after its Adam update; the inputs are seeded, so two builds can be compared output for output.
+--full adds everything below that needs runs of its own: the conv roofline (profiled eager steps), the
+measured peaks, the PMC traffic passes and the CPU baseline.
 
 Default workload: N=1 runs BASELINE.json configs[1], the headline: B=128 clips of one 224x224 RGB
 frame + one 257x300 log-spectrogram; ResNet-18 vision + ResNet-18 audio trunks (bf16 MFMA, fp32
@@ -24,7 +33,7 @@ Adam (lr 4e-6).  The audio trunk runs once per clip for both views unless --twov
 twoview.py); a clip counts once however many frames/views it has.
 
 Inputs are synthetic and already resident in HBM when the timed region starts; weights are
-random-init (no checkpoints).  Prints ONE JSON line on rank 0.  `roofline` is for the dominant
+random-init (no checkpoints).  Prints ONE JSON line on rank 0.  With --full: `roofline` is for the dominant
 kernel family (the implicit-GEMM convolutions), measured live with HIP events around every conv
 launch of eager steps run right after the timed region: achieved = algorithmic conv FLOPs / summed
 kernel time; `traffic` = PMC-measured HBM bytes per conv launch, measured live by two rocprofv3
@@ -261,6 +270,32 @@ def cpu_baseline(workload: str, budget_s: float = 20.0):
                       f"{n}; fwd_loss_clips_per_s: forward + CE only (configs[0]), median of {n_f}"}
 
 
+DUMP_SAMPLE = 1 << 21  # elements of the flat gradient / parameters kept by --dump-outputs (8 MiB each as float32)
+
+
+def dump_outputs(out_dir, step, loss):
+    """What the last timed step left its caller, as <out_dir>/<name>.npy (float32): the returned loss tensor, and
+    the flat gradient and the updated flat parameters at DUMP_SAMPLE fixed positions (seeded, sorted, the same in
+    every run; all of them where the buffers are smaller)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    n = step.flat.n_train
+    if n > DUMP_SAMPLE:
+        idx = torch.randperm(n, generator=torch.Generator().manual_seed(1234))[:DUMP_SAMPLE].sort().values
+    else:
+        idx = torch.arange(n)
+    on_dev = idx.to(step.grad.device)
+    arrays = {
+        "loss": loss.detach().float().reshape(-1).cpu(),
+        "grad": step.grad[:n].index_select(0, on_dev).float().cpu(),
+        "params": step.flat.flat[:n].detach().index_select(0, on_dev).float().cpu(),
+        "sample_index": idx.double(),
+    }
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.numpy())
+
+
 def eager_copy(step):
     """A view of the train step (same buffers, optimizer, engine) whose step() launches every kernel eagerly.
     Every captured form must be dropped -- world 1: _graph; world > 1: _seg_graphs (overlap schedule) or
@@ -286,6 +321,11 @@ def main():
                     "16x-repeated spectrogram batch once per view (the reference's arithmetic)")
     ap.add_argument("--tube-folded", action="store_true", help="tube: run the audio trunk over the folded "
                     "16x-repeated spectrogram batch (the reference's arithmetic) instead of once per clip")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what the last "
+                    "one computed (loss, sampled flat gradient and updated parameters) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true", help="also measure what needs runs of its own: the conv roofline "
+                    "(--prof-steps), the peaks, the PMC traffic (--traffic) and the CPU baseline; --prof-steps, --traffic, "
+                    "--traffic-out, --no-peaks, --no-cpu-baseline and --cpu-budget only shape a --full run")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-budget", type=float, default=20.0)
     ap.add_argument("--no-graph", action="store_true", help="launch every kernel eagerly instead of replaying a "
@@ -298,6 +338,8 @@ def main():
     ap.add_argument("--traffic-out", default="", help="write the traffic record (tools/traffic_summary.py format) here")
     ap.add_argument("--no-peaks", action="store_true", help="skip the in-run MFMA / HBM peak measurement")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     avt_env = check_env()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -390,29 +432,59 @@ def main():
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     loss_v = float(loss.flatten()[0])  # twoview: losses[0] = the combined loss
-    # roofline of the conv family: HIP events on the launch stream around every conv launch of a
-    # few eager steps of the same workload (kept out of the timed region above)
-    eager = eager_copy(step)
-    conc = step.engine.concurrent
-    step.engine.concurrent = False  # per-kernel durations of the conv launches, not of overlapped pairs
-    with ConvProfiler() as prof:
-        for _ in range(args.prof_steps):
-            eager.step(*inputs)
-        torch.cuda.synchronize()
-    step.engine.concurrent = conc
-    conv = prof.summary()
-    if args.prof_steps > 0 and not conv:
-        sys.exit("bench.py: the profiled eager steps launched no conv kernel (a captured graph was replayed?)")
-    peaks = None if args.no_peaks else measure_peaks(dev)
+    if args.dump_outputs and rank == 0:  # before anything below runs another step
+        dump_outputs(args.dump_outputs, step, loss)
+    conv, peaks = {}, None
+    if args.full:
+        # roofline of the conv family: HIP events on the launch stream around every conv launch of a
+        # few eager steps of the same workload (kept out of the timed region above)
+        eager = eager_copy(step)
+        conc = step.engine.concurrent
+        step.engine.concurrent = False  # per-kernel durations of the conv launches, not of overlapped pairs
+        with ConvProfiler() as prof:
+            for _ in range(args.prof_steps):
+                eager.step(*inputs)
+            torch.cuda.synchronize()
+        step.engine.concurrent = conc
+        conv = prof.summary()
+        if args.prof_steps > 0 and not conv:
+            sys.exit("bench.py: the profiled eager steps launched no conv kernel (a captured graph was replayed?)")
+        peaks = None if args.no_peaks else measure_peaks(dev)
     el = torch.tensor([elapsed], device=dev, dtype=torch.float64)
     if world > 1:
         dist.all_reduce(el, op=dist.ReduceOp.MAX)
     elapsed = el.item()
     if rank == 0:
-        ps = max(args.prof_steps, 1)
         clips = B * world * args.steps
         value = clips / elapsed
         ms_step = elapsed / args.steps * 1e3
+        rec = {
+            "metric": METRIC,
+            "value": round(value, 2),
+            "unit": "clips/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": round(ms_step, 3),
+            "higher_is_better": True,
+            "scaling": "strong" if strong else "weak",
+            "vs_baseline": None,
+            "dtype": "bf16",
+            "data": DATA,
+            "config": {"workload": workload, "global_batch": B * world, "per_gpu_batch": B,
+                       "parallelism": f"dp{world}"},
+            "backend": (backend if world > 1 else None),
+            "launch": ("eager" if args.no_graph else "hip-graph replay") + (
+                ", audio trunk on a second stream" if step.engine.concurrent else ""),
+            # SURVEY 8(d)'s secondary HBM view: clips/s x 80.8 MB algorithmic bytes per clip / (G x 8 TB/s)
+            "hbm_view_frac": round(value * ALG_BYTES_PER_CLIP / (world * HBM_PEAK_GBS * 1e9), 4)
+            if args.workload == "1frame" else None,
+            "avt_env": avt_env,
+            "loss": round(loss_v, 6),
+            "full": args.full,
+        }
+    if rank == 0 and args.full:
+        ps = max(args.prof_steps, 1)
         fl = sum(v[1] for v in conv.values())
         ms = sum(v[2] for v in conv.values())
         n_launch = sum(v[0] for v in conv.values())
@@ -436,22 +508,7 @@ def main():
             traffic = round((trec["conv_read_bytes_per_step"] + trec["conv_write_bytes_per_step"]) / lps)
         step_tflops = conv_tflop_step / (ms_step * 1e-3)
         peak_meas = peaks["mfma_32x32x16_bf16"] if peaks else None
-        rec = {
-            "metric": METRIC,
-            "value": round(value, 2),
-            "unit": "clips/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(ms_step, 3),
-            "higher_is_better": True,
-            "scaling": "strong" if strong else "weak",
-            "vs_baseline": None,
-            "dtype": "bf16",
-            "data": DATA,
-            "config": {"workload": workload, "global_batch": B * world, "per_gpu_batch": B,
-                       "parallelism": f"dp{world}"},
-            "backend": (backend if world > 1 else None),
+        rec.update({
             "roofline": {"bound": "mfma", "kernel": "conv implicit-GEMM (fwd+dgrad+wgrad)",
                          "achieved": round(achieved, 2), "peak": MFMA_BF16_PEAK_TFLOPS, "unit": "TFLOP/s",
                          "frac": round(achieved / MFMA_BF16_PEAK_TFLOPS, 4), "traffic": traffic,
@@ -467,26 +524,20 @@ def main():
                          "conv_ms_per_step": round(ms / ps, 3),
                          "measured": f"HIP events around each conv launch, {args.prof_steps} eager steps after the "
                                      "timed region"},
-            "launch": ("eager" if args.no_graph else "hip-graph replay") + (
-                ", audio trunk on a second stream" if step.engine.concurrent else ""),
             # whole step: algorithmic conv FLOPs of one step / step time (head, BN, Adam: < 1 %)
             "step_conv_tflop": round(conv_tflop_step, 4),
             "step_tflops_per_gpu": round(step_tflops, 2),
             "step_mfma_frac": round(step_tflops / MFMA_BF16_PEAK_TFLOPS, 4),
             "step_mfma_frac_vs_measured": round(step_tflops / peak_meas, 4) if peak_meas else None,
-            # SURVEY 8(d)'s secondary HBM view: clips/s x 80.8 MB algorithmic bytes per clip / (G x 8 TB/s)
-            "hbm_view_frac": round(value * ALG_BYTES_PER_CLIP / (world * HBM_PEAK_GBS * 1e9), 4)
-            if args.workload == "1frame" else None,
             "step_hbm_bytes": round(trec["step_bytes"]) if trec else None,
             "step_hbm_tbs": round(trec["step_bytes"] / (ms_step * 1e-3) / 1e12, 3) if trec else None,
             "peaks_measured": {k: round(v, 2) for k, v in peaks.items()} if peaks else None,
             "peak_units": {"mfma_*": "TFLOP/s", "hbm_copy_tbs": "TB/s (read + write)"},
-            "avt_env": avt_env,
-            "loss": round(loss_v, 6),
             "cpu_baseline": None,
-        }
+        })
         if world == 1 and not args.no_cpu_baseline:
             rec["cpu_baseline"] = cpu_baseline(args.workload, args.cpu_budget)
+    if rank == 0:
         print(json.dumps(rec), flush=True)
     if world > 1:
         dist.barrier()

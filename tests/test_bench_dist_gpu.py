@@ -2,7 +2,8 @@
 ``python -m torch.distributed.run --nproc-per-node N bench.py --gpus N``; this runs that command at N=2 on the
 box's one GPU with the test-only overrides AVT_BENCH_BACKEND=gloo and AVT_BENCH_ONE_DEVICE=1 (RCCL needs one device
 per rank; both ranks share cuda:0, as tests/test_ddp_gpu.py does).  It must print one JSON line with configs[2]'s
-sharding (global 256 -> 128 per GPU, strong scaling) and a roofline measured on eager launches."""
+sharding (global 256 -> 128 per GPU, strong scaling) and, being a --full run, a roofline measured on eager
+launches."""
 import json
 import math
 import os
@@ -29,7 +30,8 @@ def test_bench_two_ranks_prints_one_valid_line():
     env = dict(os.environ, AVT_BENCH_BACKEND="gloo", AVT_BENCH_ONE_DEVICE="1", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes", "1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(REPO, "bench.py"),
-           "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--traffic", "off", "--no-peaks"]
+           "--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--traffic", "off",
+           "--no-peaks"]
     r = subprocess.run(cmd, env=env, cwd=REPO, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
                        timeout=360)
     assert r.returncode == 0, r.stderr[-4000:]

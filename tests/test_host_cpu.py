@@ -271,6 +271,41 @@ def test_bench_eager_copy_drops_every_captured_form():
     assert calls == ["replay", "eager"] * 3, calls
 
 
+def test_bench_dump_outputs_writes_fixed_sample(tmp_path):
+    """bench.py --dump-outputs: the loss whole, the flat gradient and parameters at the same seeded positions in
+    every run, float32, within the 64 MB the option allows even at the full model's parameter count."""
+    import importlib.util
+    import types
+
+    spec = importlib.util.spec_from_file_location("avt_bench_mod", os.path.join(REPO, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+
+    n = bench.DUMP_SAMPLE + 1001  # larger than the sample: positions are drawn
+    g = torch.Generator().manual_seed(5)
+    flat = types.SimpleNamespace(n_train=n, flat=torch.randn(n + 64, generator=g))
+    step = types.SimpleNamespace(flat=flat, grad=torch.randn(n, generator=g))
+    loss = torch.tensor([0.25, 1.5])
+    dirs = [str(tmp_path / "a"), str(tmp_path / "b")]
+    for d in dirs:
+        bench.dump_outputs(d, step, loss)
+    got = {k: np.load(os.path.join(dirs[0], k + ".npy")) for k in ("loss", "grad", "params", "sample_index")}
+    assert sorted(os.listdir(dirs[0])) == sorted(k + ".npy" for k in got)
+    assert all(v.dtype in (np.float32, np.float64) for v in got.values())
+    idx = got["sample_index"].astype(np.int64)
+    assert idx.shape == (bench.DUMP_SAMPLE,) and (np.diff(idx) > 0).all() and idx[0] >= 0 and idx[-1] < n
+    assert np.array_equal(got["loss"], loss.numpy())
+    assert np.array_equal(got["grad"], step.grad.numpy()[idx])
+    assert np.array_equal(got["params"], flat.flat.numpy()[idx])
+    for k, v in got.items():
+        assert np.array_equal(v, np.load(os.path.join(dirs[1], k + ".npy"))), k
+    assert 2 * bench.DUMP_SAMPLE * 4 + bench.DUMP_SAMPLE * 8 + 64 < 64e6
+    small = types.SimpleNamespace(flat=types.SimpleNamespace(n_train=8, flat=torch.arange(12.0)),
+                                  grad=torch.arange(8.0))
+    bench.dump_outputs(str(tmp_path / "c"), small, loss[:1])
+    assert np.array_equal(np.load(str(tmp_path / "c" / "params.npy")), np.arange(8, dtype=np.float32))
+
+
 def test_h1_skip_diagnostic_needs_opt_in():
     """AVT_DIAG_H1_SKIP makes the trunks compute a different network (timing diagnostic): importing the library
     under it fails unless AVT_DIAG_WRONG_RESULTS_OK=1 is set as well."""

@@ -3,7 +3,8 @@
 # exported by `git archive <rev> | tar -x -C abtrees/<name>` and built with that tree's __graft_entry__.build()).
 # Alternates "<label>:<tree dir>:<extra bench.py args>" specs for $1 rounds with the driver's bench command
 # (--gpus 1 --steps 20 --warmup 5, plus $BENCH_ARGS), one summary line per run.
-# usage: bash tools/abtree.sh 3 "head:.:--traffic off --no-peaks" "r2:abtrees/r2:"
+# A tree whose bench.py has --full shows its conv figures only when the spec passes it (older trees always do).
+# usage: bash tools/abtree.sh 3 "head:.:--full --traffic off --no-peaks" "r2:abtrees/r2:"
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 cd "$R"
 mkdir -p gpurun_out

@@ -8,7 +8,8 @@
 #                          -> gpurun_out/prof_<tag>/ and gpurun_out/kstats_<tag>.txt (per-step kernel table)
 #   conv:<tag>:<args>      python tools/conv_bench.py <args> -> gpurun_out/conv_<tag>.log
 #   ab:<rounds>:<spec>|<spec>...   tools/ab3.sh (same-box A/B; BENCH_ARGS from the environment)
-# usage: bash tools/gpu_check.sh tests "bench:b128:" "bench:b32:--batch 32 --traffic-out gpurun_out/t32.json"
+# usage: bash tools/gpu_check.sh tests "bench:b128:" "bench:b32:--full --batch 32 --traffic-out t32.json"
+# (bench.py measures its roofline, peaks, traffic and CPU baseline only with --full)
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 cd "$R"
 mkdir -p gpurun_out
