@@ -16,7 +16,7 @@ CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_PATH = os.path.join(PKG_DIR, "libavt.so")
 # A/B measurement only: load another in-tree build of the same ABI (e.g. libavt_base.so)
 LOAD_PATH = os.environ.get("AVT_LIB_PATH", LIB_PATH)
-SOURCES = ["conv_gemm.hip", "bn.hip", "pool.hip", "head.hip", "misc.hip", "tube.hip", "eval.hip", "audio.hip", "frames.hip"]
+SOURCES = ["conv_gemm.hip", "bn.hip", "pool.hip", "head.hip", "misc.hip", "tube.hip", "conv3d_bwd.hip", "eval.hip", "audio.hip", "frames.hip"]
 
 _P = ctypes.c_void_p
 _I = ctypes.c_int
@@ -101,6 +101,13 @@ SIGNATURES = {
     "avt_conv3d_fwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "avt_video_stem_im2col": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "avt_maxpool3d_fwd": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
+    "avt_pack_conv3d_weight_dgrad": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
+    "avt_pack_conv3d_weights_dgrad_batched": (_I, [_P, _I, _I, _P]),
+    "avt_conv3d_dgrad": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "avt_conv3d_wgrad_workspace": (_Z, [_I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I]),
+    "avt_conv3d_wgrad": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _Z, _P]),
+    "avt_maxpool3d_bwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "avt_stem3d_wgrad_unfold": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
     "avt_pack3d_desc_bytes": (_Z, []),
     "avt_pack_conv3d_weights_batched": (_I, [_P, _I, _I, _I, _P]),
     "avt_pack_conv3d_weight": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),

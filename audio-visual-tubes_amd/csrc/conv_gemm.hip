@@ -1372,8 +1372,10 @@ extern "C" int avt_conv2d_dgrad_mask(const void* dy, const void* wt, void* dx, c
 // y NDHWC bf16 [N][T'][H'][W'][K] with T' = T + 2*pad_t - KT + 1 (temporal stride 1, as every
 // Conv3d of the R3D-18 built by model.py:20 after the stem) and spatial stride `stride`.
 // BN statistics are accumulated in the epilogue exactly as conv2d_fwd.
-extern "C" int avt_conv3d_fwd(const void* x, const void* wpack, void* y, double* bn_acc, int N, int T, int H, int W,
-                              int Cp, int K, int KT, int R, int S, int stride, int pad_t, int pad, void* stream) {
+// (`add`: optional [N][T'][H'][W'][K] bf16 added in the store epilogue, may alias y -- avt_conv3d_dgrad's residual)
+static int conv3d_fwd_impl(const void* x, const void* wpack, void* y, double* bn_acc, const void* add, int N, int T,
+                           int H, int W, int Cp, int K, int KT, int R, int S, int stride, int pad_t, int pad,
+                           void* stream) {
   AVT_REQUIRE(x && wpack && y, "conv3d_fwd: null pointer");
   AVT_REQUIRE(K % 64 == 0, "conv3d_fwd: K=%d must be a multiple of 64", K);
   AVT_REQUIRE(Cp % 32 == 0, "conv3d_fwd: C=%d must be a multiple of 32", Cp);
@@ -1383,7 +1385,7 @@ extern "C" int avt_conv3d_fwd(const void* x, const void* wpack, void* y, double*
   p.act = (const bf16_t*)x;
   p.wmat = (const bf16_t*)wpack;
   p.out = (bf16_t*)y;
-  p.add = nullptr;
+  p.add = (const bf16_t*)add;
   p.stats = bn_acc;
   p.IT = T; p.IH = H; p.IW = W; p.IC = Cp;
   p.OT = T + 2 * pad_t - KT + 1;
@@ -1404,6 +1406,94 @@ extern "C" int avt_conv3d_fwd(const void* x, const void* wpack, void* y, double*
   else
     launch_nt<MODE_FWD, 8, 128, 64>(p, st);
   return check_launch("conv3d_fwd");
+}
+
+extern "C" int avt_conv3d_fwd(const void* x, const void* wpack, void* y, double* bn_acc, int N, int T, int H, int W,
+                              int Cp, int K, int KT, int R, int S, int stride, int pad_t, int pad, void* stream) {
+  return conv3d_fwd_impl(x, wpack, y, bn_acc, nullptr, N, T, H, W, Cp, K, KT, R, S, stride, pad_t, pad, stream);
+}
+
+// One parity class (ph, pw) of a spatially strided Conv3d's input gradient on the tap-gather kernel's Conv3d form:
+// the 2-D class scheme (launch_glds) with the temporal taps -- the rows are the class's pixels (2h'+ph, 2w'+pw) of
+// every frame, the K loop walks the class's spatial taps times all KT temporal taps (3x3 / pad 1 / stride 2: 1, 2, 2
+// and 4 spatial taps), and the tap mask drops the frames outside the row's clip.  wt is the flipped pack of
+// avt_pack_conv3d_weight_dgrad: tap (kt, r, s) is stored at (KT-1-kt, R-1-r, S-1-s).
+template <int TN>
+static void launch_dgrad3d_class(const GemmNTParams& p, int ph, int pw, hipStream_t st) {
+  constexpr int BM = 128, BN = 64 * TN;
+  NTPipeArgsV ta{};
+  const int batch = p.M / (p.OT * p.OH * p.OW);  // clips
+  ta.act_bytes = (unsigned)((size_t)batch * p.IT * p.IH * p.IW * p.IC * 2);
+  ta.w_bytes = (unsigned)((size_t)p.Ng * p.Kg * 2);
+  ta.cls = 1;
+  ta.OHf = p.OH;
+  ta.OWf = p.OW;
+  ta.ph = ph;
+  ta.pw = pw;
+  for (int kt = 0; kt < p.KT; ++kt)
+    for (int r = 0; r < p.R; ++r)
+      for (int s = 0; s < p.S; ++s) {
+        if (((ph + p.pad - r) & 1) || ((pw + p.pad - s) & 1)) continue;
+        ta.tap_w[ta.ntaps] = ((p.KT - 1 - kt) * p.R + (p.R - 1 - r)) * p.S + (p.S - 1 - s);
+        ta.tap_dt[ta.ntaps] = p.pad_t - kt;
+        ta.tap_dy[ta.ntaps] = (ph + p.pad - r) / 2;
+        ta.tap_dx[ta.ntaps] = (pw + p.pad - s) / 2;
+        ++ta.ntaps;
+      }
+  GemmNTParams pc = p;
+  pc.OH = (p.OH - ph + 1) / 2;
+  pc.OW = (p.OW - pw + 1) / 2;
+  pc.M = batch * p.OT * pc.OH * pc.OW;
+  // a class no tap reaches is written as 0 (+ add) by an empty K loop; accumulating in place it is already final
+  if (pc.M <= 0 || (ta.ntaps == 0 && p.add != nullptr && p.add == p.out)) return;
+  ta.div_hw = make_magic((unsigned)(pc.OH * pc.OW));
+  ta.div_ow = make_magic((unsigned)pc.OW);
+  for (int k = 0; k < 4; ++k) ta.cdiv_hw[k] = ta.cdiv_ow[k] = make_magic(1u);
+  const int grid = ((pc.M + BM - 1) / BM) * (p.Ng / BN);
+  hipLaunchKernelGGL((conv_nt_pipe_kernel<MODE_DGRAD, 2, 2, 2, TN, 4, 32, true>), dim3(grid), dim3(256), 0, st, pc, ta);
+}
+
+// Conv3d input gradient (autograd's backward of conv3x3x3, models/resnet3D.py:14-20, in BasicBlock.forward 45-61):
+// dx[N][T][H][W][C] = dgrad(dy[N][T][P][Q][K], wt[C][(KT-1-kt, R-1-r, S-1-s, k)]) (+ add, which may alias dx).
+// Spatial stride 1: the forward conv of dy with the flipped, (K, C)-transposed weights and pad' = k - 1 - pad, on
+// avt_conv3d_fwd's own launch path (the three-patch halo form included).  Stride 2: the four parity classes above.
+extern "C" int avt_conv3d_dgrad(const void* dy, const void* wt, void* dx, const void* add, int N, int T, int H, int W,
+                                int C, int K, int KT, int R, int S, int stride, int pad_t, int pad, void* stream) {
+  AVT_REQUIRE(dy && wt && dx, "conv3d_dgrad: null pointer");
+  AVT_REQUIRE(C % 64 == 0 && K % 32 == 0, "conv3d_dgrad: C=%d (a multiple of 64) K=%d (of 32) unsupported", C, K);
+  AVT_REQUIRE(KT >= 1 && R >= 1 && S >= 1 && KT * R * S <= kMaxTaps, "conv3d_dgrad: at most %d taps", kMaxTaps);
+  AVT_REQUIRE(stride == 1 || stride == 2, "conv3d_dgrad: spatial stride must be 1 or 2");
+  AVT_REQUIRE(pad_t >= 0 && pad >= 0 && pad_t < KT && pad < R && pad < S, "conv3d_dgrad: padding must be below the kernel size");
+  const int To = T + 2 * pad_t - KT + 1, P = conv_out(H, R, stride, pad), Q = conv_out(W, S, stride, pad);
+  AVT_REQUIRE(N >= 1 && To >= 1 && P >= 1 && Q >= 1, "conv3d_dgrad: empty gradient");
+  if (stride == 1) {
+    AVT_REQUIRE(R == S, "conv3d_dgrad: square spatial taps only");
+    return conv3d_fwd_impl(dy, wt, dx, nullptr, add, N, To, P, Q, K, C, KT, R, S, 1, KT - 1 - pad_t, R - 1 - pad,
+                           stream);
+  }
+  AVT_REQUIRE(conv_variant() == 1, "conv3d_dgrad: needs the LDS-DMA conv kernels (AVT_CONV_VARIANT=1)");
+  GemmNTParams p{};
+  p.act = (const bf16_t*)dy;
+  p.wmat = (const bf16_t*)wt;
+  p.out = (bf16_t*)dx;
+  p.add = (const bf16_t*)add;
+  p.IT = To; p.IH = P; p.IW = Q; p.IC = K;
+  p.OT = T; p.OH = H; p.OW = W;
+  p.M = N * T * H * W;
+  p.Ng = C;
+  p.Kg = KT * R * S * K;
+  p.KT = KT; p.R = R; p.S = S; p.stride = stride; p.pad = pad; p.pad_t = pad_t;
+  AVT_REQUIRE((size_t)p.M * C * 2 < (1ull << 31) && (size_t)N * To * P * Q * K * 2 < (1ull << 31),
+              "conv3d_dgrad: activation tensors must stay below 2 GiB (32-bit buffer offsets)");
+  hipStream_t st = (hipStream_t)stream;
+  for (int ph = 0; ph < 2; ++ph)
+    for (int pw = 0; pw < 2; ++pw) {
+      if (C % 128 == 0)
+        launch_dgrad3d_class<2>(p, ph, pw, st);
+      else
+        launch_dgrad3d_class<1>(p, ph, pw, st);
+    }
+  return check_launch("conv3d_dgrad");
 }
 
 // wgrad launch plan: tile shape, split-K and (pipelined kernel) the fp32 partial slab it needs.

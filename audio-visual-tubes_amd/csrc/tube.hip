@@ -225,6 +225,129 @@ __global__ __launch_bounds__(256) void maxpool3d_k3s2p1_kernel(const bf16_t* __r
   }
 }
 
+// Conv3d dgrad operand: out[c][tf*K + k] = bf16(w[k][c][T-1-tf]) (T = KT*R*S taps; the linear flip reverses kt, r and s
+// at once) -- the fold-0 layout with K and C swapped and the taps reversed, so that the stride-1 input gradient is
+// avt_conv3d_fwd's own conv of dy.  One block per (c, 64 filters): the 64 tap runs of w read through LDS, 128-byte
+// bf16 runs written.  K % 64 == 0, T <= 64.
+__device__ __forceinline__ void pack_conv3d_dgrad_tile(const float* __restrict__ w, bf16_t* __restrict__ out, int K,
+                                                       int C, int T, int blk, float* tile) {
+  const int kb = K / 64;
+  const int c = blk / kb, k0 = (blk - c * kb) * 64;
+  __syncthreads();
+  for (int i = threadIdx.x; i < 64 * T; i += blockDim.x) {
+    const int kk = i / T, t = i - kk * T;
+    tile[i] = w[((size_t)(k0 + kk) * C + c) * T + t];
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < 64 * T; i += blockDim.x) {
+    const int tf = i >> 6, kk = i & 63;
+    out[((size_t)c * T + tf) * K + k0 + kk] = f2bf(tile[kk * T + (T - 1 - tf)]);
+  }
+}
+
+__global__ __launch_bounds__(256) void pack_conv3d_dgrad_kernel(const float* __restrict__ w, bf16_t* __restrict__ out,
+                                                                int K, int C, int T) {
+  __shared__ float tile[64 * 64];
+  const int nblk = C * (K / 64);
+  for (int b = blockIdx.x; b < nblk; b += gridDim.x) pack_conv3d_dgrad_tile(w, out, K, C, T, b, tile);
+}
+
+// the same for every record of a Pack3dDesc table in one launch (blockIdx.y = conv; out = that conv's dgrad operand)
+__global__ __launch_bounds__(256) void pack_conv3d_dgrad_batched_kernel(const Pack3dDesc* __restrict__ descs) {
+  __shared__ float tile[64 * 64];
+  const Pack3dDesc d = descs[blockIdx.y];
+  const int nblk = d.C * (d.K / 64);
+  for (int b = blockIdx.x; b < nblk; b += gridDim.x) pack_conv3d_dgrad_tile(d.w, d.out, d.K, d.C, d.T, b, tile);
+}
+
+// Backward of maxpool3d_k3s2p1_kernel in gather form (no atomics): one thread per INPUT voxel and 8 channels sums the
+// gy of the (at most 2 x 2 x 2) windows that hold it and whose winner it is.  The winner is recomputed from x as the
+// forward takes it: the first maximum in (t, h, w) scan order (a NaN tap wins and stays) -- torch's CPU max_pool3d
+// choice, which decides where the gradient of the ReLU output's all-zero windows goes.  fp32 sum, one bf16 rounding.
+__global__ __launch_bounds__(256) void maxpool3d_k3s2p1_bwd_kernel(const bf16_t* __restrict__ gy,
+                                                                   const bf16_t* __restrict__ x,
+                                                                   bf16_t* __restrict__ gx, int N, int T, int H, int W,
+                                                                   int C, int To, int Ho, int Wo) {
+  const int cv = C / 8;
+  const long long total = (long long)N * T * H * W * cv;
+  const u32x4* x4 = reinterpret_cast<const u32x4*>(x);
+  const u32x4* g4 = reinterpret_cast<const u32x4*>(gy);
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total;
+       i += (long long)gridDim.x * blockDim.x) {
+    const int c8 = (int)(i % cv);
+    long long r = i / cv;
+    const int w = (int)(r % W);
+    r /= W;
+    const int h = (int)(r % H);
+    r /= H;
+    const int t = (int)(r % T);
+    const int n = (int)(r / T);
+    float sum[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) sum[e] = 0.f;
+    // windows holding coordinate v: o with 2o - 1 <= v <= 2o + 1
+    for (int to = t / 2; to <= (t + 1) / 2 && to < To; ++to)
+      for (int ho = h / 2; ho <= (h + 1) / 2 && ho < Ho; ++ho)
+        for (int wo = w / 2; wo <= (w + 1) / 2 && wo < Wo; ++wo) {
+          float m[8];
+          int win[8];  // the winner's tap index (dt * 3 + dh) * 3 + dw
+#pragma unroll
+          for (int e = 0; e < 8; ++e) {
+            m[e] = -__builtin_inff();
+            win[e] = -1;
+          }
+          for (int dt = 0; dt < 3; ++dt) {
+            const int tt = 2 * to - 1 + dt;
+            if (tt < 0 || tt >= T) continue;
+            for (int dh = 0; dh < 3; ++dh) {
+              const int hh = 2 * ho - 1 + dh;
+              if (hh < 0 || hh >= H) continue;
+              for (int dw = 0; dw < 3; ++dw) {
+                const int ww = 2 * wo - 1 + dw;
+                if (ww < 0 || ww >= W) continue;
+                const u32x4 v = x4[((((long long)n * T + tt) * H + hh) * W + ww) * cv + c8];
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                  const float f = bf2f((bf16_t)((e & 1) ? (v[e >> 1] >> 16) : (v[e >> 1] & 0xffff)));
+                  if ((f > m[e] || f != f) && m[e] == m[e]) {
+                    m[e] = f;
+                    win[e] = (dt * 3 + dh) * 3 + dw;
+                  }
+                }
+              }
+            }
+          }
+          const int mine = ((t - 2 * to + 1) * 3 + (h - 2 * ho + 1)) * 3 + (w - 2 * wo + 1);
+          const u32x4 g = g4[((((long long)n * To + to) * Ho + ho) * Wo + wo) * cv + c8];
+#pragma unroll
+          for (int e = 0; e < 8; ++e)
+            if (win[e] == mine) sum[e] += bf2f((bf16_t)((e & 1) ? (g[e >> 1] >> 16) : (g[e >> 1] & 0xffff)));
+        }
+    u32x4 o;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) o[q] = pack2(sum[2 * q], sum[2 * q + 1]);
+    reinterpret_cast<u32x4*>(gx)[i] = o;
+  }
+}
+
+// dw[k][c][kt][r][s] += dwf[k][r][s][kt*4 + c]: the folded stem's 2-D weight gradient (32 channels per (r, s), the
+// layout of avt_pack_conv3d_weight fold 1) back to the Parameter's OIDHW layout
+__global__ __launch_bounds__(256) void stem3d_wgrad_unfold_kernel(const float* __restrict__ dwf, float* __restrict__ dw,
+                                                                  int K, int C, int KT, int R, int S) {
+  const int total = K * C * KT * R * S;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
+    int j = i;
+    const int s = j % S;
+    j /= S;
+    const int r = j % R;
+    j /= R;
+    const int kt = j % KT;
+    j /= KT;
+    const int c = j % C, k = j / C;
+    dw[i] += dwf[((size_t)(k * R + r) * S + s) * 32 + kt * 4 + c];
+  }
+}
+
 static int grid_for(long long n) {
   long long g = (n + 255) / 256;
   if (g > 8192) g = 8192;
@@ -277,6 +400,51 @@ extern "C" int avt_maxpool3d_fwd(const void* x, void* y, int N, int T, int H, in
   hipLaunchKernelGGL(maxpool3d_k3s2p1_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x,
                      (bf16_t*)y, N, T, H, W, C, To, Ho, Wo);
   return check_launch("maxpool3d_fwd");
+}
+
+// w: fp32 OIDHW [K][C][KT][R][S] -> out bf16 [C][(KT-1-kt, R-1-r, S-1-s, k)]: the operand of avt_conv3d_dgrad
+extern "C" int avt_pack_conv3d_weight_dgrad(const float* w, void* out, int K, int C, int KT, int R, int S,
+                                            void* stream) {
+  AVT_REQUIRE(w && out, "pack_conv3d_weight_dgrad: null pointer");
+  AVT_REQUIRE(K >= 64 && K % 64 == 0 && C >= 1 && KT >= 1 && R >= 1 && S >= 1 && KT * R * S <= 64,
+              "pack_conv3d_weight_dgrad: K=%d (a multiple of 64), %d taps (<= 64)", K, KT * R * S);
+  const int nblk = C * (K / 64);
+  hipLaunchKernelGGL(pack_conv3d_dgrad_kernel, dim3(nblk < 8192 ? nblk : 8192), dim3(256), 0, (hipStream_t)stream, w,
+                     (bf16_t*)out, K, C, KT * R * S);
+  return check_launch("pack_conv3d_weight_dgrad");
+}
+
+// descs: device array of n avt_pack3d_desc_bytes() records whose `out` is the conv's dgrad operand [C][T*K] (K % 64
+// == 0, T <= 64 -- the caller's to keep: the table is on the device); max_blocks = the largest C * K / 64
+extern "C" int avt_pack_conv3d_weights_dgrad_batched(const void* descs, int n, int max_blocks, void* stream) {
+  AVT_REQUIRE(descs && n > 0 && max_blocks > 0, "pack_conv3d_weights_dgrad_batched: bad arguments");
+  hipLaunchKernelGGL(pack_conv3d_dgrad_batched_kernel, dim3(max_blocks < 2048 ? max_blocks : 2048, n), dim3(256), 0,
+                     (hipStream_t)stream, (const Pack3dDesc*)descs);
+  return check_launch("pack_conv3d_weights_dgrad_batched");
+}
+
+// gx bf16 [N][T][H][W][C] = backward of avt_maxpool3d_fwd(x) under gy bf16 [N][To][Ho][Wo][C]
+extern "C" int avt_maxpool3d_bwd(const void* gy, const void* x, const void* y, void* gx, int N, int T, int H, int W,
+                                 int C, void* stream) {
+  (void)y;  // the winner is recomputed from x (ties: the first maximum), y is not read
+  AVT_REQUIRE(gy && x && gx, "maxpool3d_bwd: null pointer");
+  AVT_REQUIRE(N >= 0 && T >= 1 && H >= 1 && W >= 1 && C >= 8 && C % 8 == 0,
+              "maxpool3d_bwd: N=%d T=%d H=%d W=%d C=%d (C a multiple of 8)", N, T, H, W, C);
+  const int To = (T - 1) / 2 + 1, Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
+  const long long n = (long long)N * T * H * W * (C / 8);
+  if (n == 0) return AVT_OK;
+  hipLaunchKernelGGL(maxpool3d_k3s2p1_bwd_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream,
+                     (const bf16_t*)gy, (const bf16_t*)x, (bf16_t*)gx, N, T, H, W, C, To, Ho, Wo);
+  return check_launch("maxpool3d_bwd");
+}
+
+extern "C" int avt_stem3d_wgrad_unfold(const float* dwf, float* dw, int K, int C, int KT, int R, int S, void* stream) {
+  AVT_REQUIRE(dwf && dw, "stem3d_wgrad_unfold: null pointer");
+  AVT_REQUIRE(K >= 1 && C >= 1 && C <= 4 && KT >= 1 && KT <= 8 && R >= 1 && S >= 1,
+              "stem3d_wgrad_unfold: need C <= 4 and KT <= 8 (the 32-channel fold)");
+  hipLaunchKernelGGL(stem3d_wgrad_unfold_kernel, dim3(grid_for((long long)K * C * KT * R * S)), dim3(256), 0,
+                     (hipStream_t)stream, dwf, dw, K, C, KT, R, S);
+  return check_launch("stem3d_wgrad_unfold");
 }
 
 extern "C" size_t avt_pack3d_desc_bytes(void) { return sizeof(Pack3dDesc); }

@@ -6,8 +6,14 @@ reference's weights and ``state_dict`` keys/shapes match (``vidnet.conv1.weight`
 ``vidnet.layerL.B.downsample.{0,1}.*``, ``vidnet.fc.*``).  Inside FullModel the compute runs in its
 engine (tube.py); called on its own (``FullModel.vidnet(video)`` or a standalone
 ``generate_model(18, ...)``, with the stem max-pool or without) the same kernels run through tube.R3DEngine and return
-the ``fc`` logits as resnet3D.ResNet.forward does (resnet3D.py:197-213).  Forward only: the build
-computes no gradients for the video trunk (FullModel detaches it), so a call that would need them raises.
+the ``fc`` logits as resnet3D.ResNet.forward does (resnet3D.py:197-213).
+
+Forward only by default: FullModel detaches the video trunk, so a call that would need gradients raises.  A
+standalone module becomes trainable with ``net.enable_backward()`` (fine-tuning or pre-training the trunk the
+reference loads Kinetics weights into, train_3D.py:89): every parameter then receives its gradient from libavt's
+Conv3d dgrad / wgrad, BatchNorm and max-pool backward kernels (tube.R3DTrunk.backward) through one
+``autograd.Function``, and ``torch.optim`` optimizers work on ``net.parameters()`` (views of the flat store).  No
+gradient is computed for the video itself.
 """
 from __future__ import annotations
 
@@ -75,6 +81,7 @@ class ResNet(nn.Module):
         self._avt_parent = None  # (weakref to the owning FullModel, prefix) once adopted
         self._avt_engine = None
         self._own_flat = None  # a standalone module's flat storage, created at its first .to() / forward
+        self._avt_backward = False  # enable_backward(): every parameter trainable (standalone modules only)
 
     def _make_layer(self, block, planes, blocks, stride=1):
         downsample = None  # built before the block, as resnet3D.py:169-184 (RNG order)
@@ -101,8 +108,25 @@ class ResNet(nn.Module):
         from .engine import FlatStore
 
         if self._own_flat is None:
-            self._own_flat = FlatStore(self, lambda n: False)  # nothing of the video trunk is trained here
+            # nothing of the video trunk is trained unless enable_backward() was called (then: every parameter)
+            self._own_flat = FlatStore(self, (lambda n: True) if self._avt_backward else (lambda n: False))
         return self._own_flat
+
+    def enable_backward(self):
+        """Make this standalone trunk trainable: its flat store is rebuilt with every parameter in the trainable
+        segment, and grad-mode calls in train mode go through the backward kernels.  Raises on a trunk adopted by a
+        FullModel (the reference detaches that trunk, model.py:14; the tube step computes no video gradients)."""
+        if self._avt_parent is not None:
+            raise RuntimeError("avt: enable_backward() is for a standalone R3D trunk; FullModel.vidnet is detached "
+                               "(model.py:14) and stays forward-only")
+        if not self._avt_backward:
+            self._avt_backward = True
+            if self._own_flat is not None:  # rebuild from the current parameter values (and device)
+                from .engine import FlatStore
+
+                self._own_flat = FlatStore(self, lambda n: True)
+            self._avt_engine = None
+        return self
 
     def _apply(self, fn, recurse=True):
         if self._avt_parent is not None and self._avt_parent[0]() is not None:
@@ -116,9 +140,24 @@ class ResNet(nn.Module):
         """resnet3D.ResNet.forward (resnet3D.py:197-213): x fp32 [b,3,t,H,W] -> fc logits [b, n_classes]."""
         from .tube import R3DEngine
 
-        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
+        need_grad = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters()))
+        if need_grad and x.requires_grad:
+            raise NotImplementedError("avt: no input gradient is computed for the video of the R3D trunk; pass a video "
+                                      "tensor that does not require grad")
+        if need_grad and not (self._avt_backward and self._avt_parent is None):
             raise NotImplementedError("avt: the R3D trunk is forward-only in this build (FullModel detaches it); "
-                                      "call it under torch.no_grad() or with requires_grad_(False) parameters")
+                                      "call it under torch.no_grad() or with requires_grad_(False) parameters.  A "
+                                      "standalone trunk becomes trainable after net.enable_backward().")
+        if need_grad and not self.training:
+            raise NotImplementedError("avt: gradients through an eval-mode trunk are not computed (train-mode "
+                                      "BatchNorm only)")
+        if need_grad:
+            flat = self._flat_store()
+            if self._avt_engine is None or self._avt_engine.flat is not flat or not self._avt_engine.with_backward:
+                self._avt_engine = R3DEngine(flat, "", max_pool=not self.no_max_pool, with_backward=True)
+            named = dict(self.named_parameters())
+            names = [n for n in flat.pnames if named[n].requires_grad]
+            return _R3DFunction.apply(self._avt_engine, names, x, *[named[n] for n in names])
         if self._avt_parent is not None:
             parent, prefix = self._avt_parent[0](), self._avt_parent[1]
             if parent is None or getattr(parent, prefix.rstrip("."), None) is not self:
@@ -129,6 +168,31 @@ class ResNet(nn.Module):
         if self._avt_engine is None or self._avt_engine.flat is not flat:
             self._avt_engine = R3DEngine(flat, prefix, max_pool=not self.no_max_pool)
         return self._avt_engine.forward(x, self.training)
+
+
+class _R3DFunction(torch.autograd.Function):
+    """Bridge of a trainable standalone trunk into autograd (as model._TrunkFunction): forward keeps the engine's
+    tape, backward returns the per-parameter views of one flat gradient buffer."""
+
+    @staticmethod
+    def forward(ctx, engine, names, x, *params):
+        out, tape = engine.forward(x, True, tape=True)
+        ctx.engine, ctx.tape, ctx.names = engine, tape, names
+        ctx.set_materialize_grads(False)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        if g is None:
+            return (None, None, None) + (None,) * len(ctx.names)
+        if ctx.tape is None:
+            raise RuntimeError("avt: second backward through a trunk forward")
+        flat = ctx.engine.flat
+        gflat = torch.zeros(flat.n_train, device=g.device, dtype=torch.float32)
+        ctx.engine.backward(ctx.tape, g, gflat)
+        ctx.tape = None
+        views = flat.param_grad_views(gflat)
+        return (None, None, None) + tuple(views[n] for n in ctx.names)
 
 
 def generate_model(model_depth, **kwargs):

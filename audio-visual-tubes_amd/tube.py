@@ -1,4 +1,5 @@
-"""3-D tube step (BASELINE config 4) on libavt: FullModel = R3D-18 video trunk (forward only) +
+"""3-D tube step (BASELINE config 4) on libavt: FullModel = R3D-18 video trunk (forward only inside FullModel;
+trainable on its own after ``resnet3D.ResNet.enable_backward()``: R3DTrunk.backward / R3DEngine.backward) +
 audio ResNet-18 (forward + backward) + the hard-way attention head.
 
 Restates model.py:17-60 and the train_3D.py step (126-138):
@@ -65,8 +66,8 @@ class Conv3dSpec:
 
 
 class R3DTrunk:
-    """resnet3D ResNet(BasicBlock, [2,2,2,2]) up to layer4, forward only; no_max_pool=True (FullModel, model.py:20)
-    unless max_pool (the stem's MaxPool3d(3, 2, 1), resnet3D.py:129, 200-201)."""
+    """resnet3D ResNet(BasicBlock, [2,2,2,2]) up to layer4, forward and (from a tape) backward; no_max_pool=True
+    (FullModel, model.py:20) unless max_pool (the stem's MaxPool3d(3, 2, 1), resnet3D.py:129, 200-201)."""
 
     def __init__(self, prefix: str, max_pool: bool = False):
         self.prefix = prefix
@@ -129,19 +130,26 @@ class R3DTrunk:
         stats = _bn_finalize(y, acc, y.numel() // spec.cout, bn, store, training)
         return y, stats, Ho, Wo
 
-    def forward(self, video: torch.Tensor, store, training: bool) -> torch.Tensor:
-        """video fp32 [b,3,T,H,W] -> layer4 map as '(b t) h w c' bf16 [b*T, h, w, 512]."""
+    def forward(self, video: torch.Tensor, store, training: bool, tape: bool = False):
+        """video fp32 [b,3,T,H,W] -> layer4 map as '(b t) h w c' bf16 [b*T, h, w, 512].  tape=True: returns
+        (map, tape) with everything ``backward`` reads kept alive (the folded input, the stem's c0/s0/h0 and per
+        block x, c1, s1, h1, c2, s2, cd, sd, out); without it the launches and the frees are unchanged."""
+        tp = {"blocks": []} if tape else None
         video = video.contiguous().float()
         b, C, T, H, W = video.shape
         if C != 3:
             raise ValueError(f"avt: expected video [b,3,t,H,W], got {tuple(video.shape)}")
         x = torch.empty(b, T, H, W, 32, device=video.device, dtype=torch.bfloat16)
         call("avt_video_stem_im2col", P(video), P(x), b, C, T, H, W, self.stem.kt, self.stem.pad_t, stream_ptr())
+        if tape:
+            tp.update(b=b, x=x, dims=(T, H, W))
         c0, s0, H, W = self._conv(x, b, T, H, W, self.stem, self.bn1, store, training)
         del x
         rows = c0.numel() // 64
         h = torch.empty_like(c0)
         call("avt_bn_apply", P(c0), P(s0[0]), P(s0[1]), None, None, None, P(h), rows, 64, 1, stream_ptr())
+        if tape:
+            tp.update(c0=c0, s0=s0, h0=h, dims0=(T, H, W))
         del c0
         if self.max_pool:  # resnet3D.py:200-201
             To, Ho, Wo = (T - 1) // 2 + 1, (H - 1) // 2 + 1, (W - 1) // 2 + 1
@@ -154,18 +162,122 @@ class R3DTrunk:
             K = c1.shape[-1]
             rows = c1.numel() // K
             call("avt_bn_apply", P(c1), P(s1[0]), P(s1[1]), None, None, None, P(h1), rows, K, 1, stream_ptr())
+            if tape:
+                tp["blocks"].append(dict(x=h, c1=c1, s1=s1, h1=h1, dims=(T, H, W, Ho, Wo)))
             del c1
             c2, s2, _, _ = self._conv(h1, b, T, Ho, Wo, blk["conv2"], blk["bn2"], store, training)
             del h1
             out = torch.empty_like(c2)
+            cd = sd = None
+            if tape:
+                tp["blocks"][-1].update(c2=c2, s2=s2, out=out)
             if blk["down"] is not None:
                 cd, sd, _, _ = self._conv(h, b, T, H, W, blk["down"], blk["bnd"], store, training)
+                if tape:
+                    tp["blocks"][-1].update(cd=cd, sd=sd)
                 call("avt_bn_apply", P(c2), P(s2[0]), P(s2[1]), P(cd), P(sd[0]), P(sd[1]), P(out), rows, K, 1,
                      stream_ptr())
             else:
                 call("avt_bn_apply", P(c2), P(s2[0]), P(s2[1]), P(h), None, None, P(out), rows, K, 1, stream_ptr())
             h, H, W = out, Ho, Wo
-        return h
+        return (h, tp) if tape else h
+
+    # ------------------------------------------------------------------ backward
+    @staticmethod
+    def _bn_bwd(g, y, xc, stats, bn: BNSpec, store, gmask_out=None):
+        """avt_bn_bwd: g' = g * [y > 0] (y None: no mask) -> the gradient of the pre-BN activation xc; d(gamma, beta)."""
+        rows = xc.numel() // bn.c
+        gc = torch.empty_like(xc)
+        call("avt_bn_bwd", P(g), P(y), P(xc), P(stats[2]), P(stats[3]), P(store.param(bn.prefix + ".weight")),
+             P(store.grad(bn.prefix + ".weight")), P(store.grad(bn.prefix + ".bias")), P(gc), P(gmask_out),
+             P(store.stat_acc(bn, "bwd", rows)), rows, bn.c, stream_ptr())
+        return gc
+
+    @staticmethod
+    def _bn_relu_bwd(g, xc, stats, bn: BNSpec, store):
+        """bn -> relu backward, the mask recomputed from (xc, scale, shift) as the forward's avt_bn_apply made it."""
+        rows = xc.numel() // bn.c
+        gc = torch.empty_like(xc)
+        call("avt_bn_relu_bwd", P(g), P(xc), P(stats[0]), P(stats[1]), P(stats[2]), P(stats[3]),
+             P(store.param(bn.prefix + ".weight")), P(store.grad(bn.prefix + ".weight")),
+             P(store.grad(bn.prefix + ".bias")), P(gc), P(store.stat_acc(bn, "bwd", rows)), rows, bn.c, stream_ptr())
+        return gc
+
+    @staticmethod
+    def _wgrad(x, gy, b, T, H, W, spec: Conv3dSpec, store):
+        """dw (fp32 OIDHW view of the flat gradient) += the conv's weight gradient."""
+        dw = store.grad(spec.name)
+        ev = ConvProfiler.begin()
+        if spec.kt == 1:  # 1x1x1 downsample: a 2-D wgrad over the b*T frames ([K][1][1][C] == OIDHW [K][C][1][1][1])
+            wsb = int(query("avt_conv2d_wgrad_workspace", b * T, H, W, spec.cin, spec.cin, spec.cout, spec.k, spec.k,
+                            spec.stride, spec.pad))
+            ws = torch.empty(max(wsb, 16), device=x.device, dtype=torch.uint8)
+            call("avt_conv2d_wgrad", P(x), P(gy), P(dw), b * T, H, W, spec.cin, spec.cin, spec.cout, spec.k, spec.k,
+                 spec.stride, spec.pad, P(ws), wsb, stream_ptr())
+        else:
+            wsb = int(query("avt_conv3d_wgrad_workspace", b, T, H, W, spec.cin, spec.cout, spec.kt, spec.k, spec.k,
+                            spec.stride, spec.pad_t, spec.pad))
+            ws = torch.empty(max(wsb, 16), device=x.device, dtype=torch.uint8)
+            call("avt_conv3d_wgrad", P(x), P(gy), P(dw), b, T, H, W, spec.cin, spec.cout, spec.kt, spec.k, spec.k,
+                 spec.stride, spec.pad_t, spec.pad, P(ws), wsb, stream_ptr())
+        ConvProfiler.end(ev, "wgrad3d", 2.0 * gy.numel() * spec.kt * spec.k * spec.k * spec.cin,
+                         2.0 * (x.numel() + gy.numel()) + 8.0 * dw.numel())
+
+    @staticmethod
+    def _dgrad(gy, b, T, H, W, spec: Conv3dSpec, store, add=None):
+        """Input gradient [b*T, H, W, cin] of a 3x3x3 conv (+ add, which may be the result tensor itself)."""
+        wt = store.packed3d_t(spec)
+        gx = torch.empty(b * T, H, W, spec.cin, device=gy.device, dtype=torch.bfloat16)
+        ev = ConvProfiler.begin()
+        call("avt_conv3d_dgrad", P(gy), P(wt), P(gx), P(add), b, T, H, W, spec.cin, spec.cout, spec.kt, spec.k, spec.k,
+             spec.stride, spec.pad_t, spec.pad, stream_ptr())
+        ConvProfiler.end(ev, "dgrad3d", 2.0 * gy.numel() * spec.kt * spec.k * spec.k * spec.cin,
+                         2.0 * (gy.numel() + wt.numel() + gx.numel()))
+        return gx
+
+    def backward(self, tape, g: torch.Tensor, store) -> None:
+        """g bf16 [b*T, h, w, 512] = d(loss)/d(layer4 map) -> the trunk's parameter gradients, accumulated into
+        store.grad(name) (zeroed by the caller).  Blocks in reverse, unfused (autograd through BasicBlock.forward,
+        resnet3D.py:45-61): bn2 (+ downsample.1) backward, conv2 wgrad + dgrad, bn1+relu backward, conv1 wgrad + dgrad
+        with the residual gradient (identity: added in the dgrad's store; strided block: the in-place 2-D dgrad of
+        the 1x1x1 downsample), then the stem's max-pool / BN+ReLU backward and its folded weight gradient.  No
+        input gradient is computed for the video."""
+        b = tape["b"]
+        for blk, tb in zip(reversed(self.blocks), reversed(tape["blocks"])):
+            T, H, W, Ho, Wo = tb["dims"]
+            gm = torch.empty_like(g)  # g * [out > 0]: shared by bn2, downsample.1 and the identity residual
+            gc2 = self._bn_bwd(g, tb["out"], tb["c2"], tb["s2"], blk["bn2"], store, gmask_out=gm)
+            self._wgrad(tb["h1"], gc2, b, T, Ho, Wo, blk["conv2"], store)
+            gh1 = self._dgrad(gc2, b, T, Ho, Wo, blk["conv2"], store)
+            del gc2
+            gc1 = self._bn_relu_bwd(gh1, tb["c1"], tb["s1"], blk["bn1"], store)
+            del gh1
+            self._wgrad(tb["x"], gc1, b, T, H, W, blk["conv1"], store)
+            if blk["down"] is not None:
+                gcd = self._bn_bwd(gm, None, tb["cd"], tb["sd"], blk["bnd"], store)
+                self._wgrad(tb["x"], gcd, b, T, H, W, blk["down"], store)
+                g = self._dgrad(gc1, b, T, H, W, blk["conv1"], store)
+                dn = blk["down"]
+                call("avt_conv2d_dgrad", P(gcd), P(store.packed3d_t(dn)), P(g), P(g), b * T, H, W, dn.cin, dn.cout,
+                     dn.k, dn.k, dn.stride, dn.pad, stream_ptr())
+            else:
+                g = self._dgrad(gc1, b, T, H, W, blk["conv1"], store, add=gm)
+        T, H, W = tape["dims0"]
+        if self.max_pool:  # resnet3D.py:200-201
+            gp = torch.empty_like(tape["h0"])
+            call("avt_maxpool3d_bwd", P(g), P(tape["h0"]), None, P(gp), b, T, H, W, 64, stream_ptr())
+            g = gp
+        gc0 = self._bn_relu_bwd(g, tape["c0"], tape["s0"], self.bn1, store)
+        # the stem's weight gradient in its folded layout: a 2-D wgrad over the 32-channel im2col input, unfolded
+        st, x = self.stem, tape["x"]
+        Ti, Hi, Wi = tape["dims"]
+        dwf = torch.zeros(st.cout, st.k, st.k, 32, device=g.device, dtype=torch.float32)
+        wsb = int(query("avt_conv2d_wgrad_workspace", b * Ti, Hi, Wi, 32, 32, st.cout, st.k, st.k, st.stride, st.pad))
+        ws = torch.empty(max(wsb, 16), device=g.device, dtype=torch.uint8)
+        call("avt_conv2d_wgrad", P(x), P(gc0), P(dwf), b * Ti, Hi, Wi, 32, 32, st.cout, st.k, st.k, st.stride, st.pad,
+             P(ws), wsb, stream_ptr())
+        call("avt_stem3d_wgrad_unfold", P(dwf), P(store.grad(st.name)), st.cout, st.cin, st.kt, st.k, st.k,
+             stream_ptr())
 
 
 def _alloc_packs3d(engine, dev):
@@ -184,6 +296,20 @@ def _alloc_packs3d(engine, dev):
     assert descs and len(descs[0]) == int(query("avt_pack3d_desc_bytes"))
     engine._pack3d_table = torch.frombuffer(bytearray(b"".join(descs)), dtype=torch.uint8).to(dev)
     engine._pack3d_n, engine._pack3d_max = len(descs), (max_k, max_row)
+    engine._pack3d_t_table = None
+    if getattr(engine, "with_backward", False):  # the dgrad operands [cin][taps * cout] of the same convs
+        descs, max_blocks = [], 1
+        for spec in engine.vid.convs():
+            if spec.stem:
+                continue
+            t = spec.kt * spec.k * spec.k
+            wt = torch.empty(spec.cin, t * spec.cout, device=dev, dtype=torch.bfloat16)
+            engine.packs3d_t[spec.name] = wt
+            descs.append(struct.pack("<QQiiii", engine.flat.raw(spec.name).data_ptr(), wt.data_ptr(), spec.cout,
+                                     spec.cin, t, 0))
+            max_blocks = max(max_blocks, spec.cin * (spec.cout // 64))
+        engine._pack3d_t_table = torch.frombuffer(bytearray(b"".join(descs)), dtype=torch.uint8).to(dev)
+        engine._pack3d_t_n, engine._pack3d_t_blocks = len(descs), max_blocks
 
 
 def _pack3d(engine):
@@ -194,11 +320,17 @@ def _pack3d(engine):
          stem.kt, stem.k, stem.k, 1, stream_ptr())
     call("avt_pack_conv3d_weights_batched", P(engine._pack3d_table), engine._pack3d_n, *engine._pack3d_max,
          stream_ptr())
+    if engine._pack3d_t_table is not None:  # a trainable trunk: the dgrad operands too (one more launch)
+        call("avt_pack_conv3d_weights_dgrad_batched", P(engine._pack3d_t_table), engine._pack3d_t_n,
+             engine._pack3d_t_blocks, stream_ptr())
 
 
 class _TubeStore(_EngineStore):
     def packed3d(self, spec: Conv3dSpec):
         return self.e.packs3d[spec.name]
+
+    def packed3d_t(self, spec: Conv3dSpec):
+        return self.e.packs3d_t[spec.name]
 
 
 class TubeEngine(AVEngine):
@@ -329,11 +461,15 @@ class R3DEngine(AVEngine):
     """The R3D-18 trunk called on its own -- ``FullModel.vidnet(video)`` or a standalone
     ``resnet3D.generate_model(18, ...)(video)`` (resnet3D.py:197-213; with or without the stem max-pool): the conv stem ..
     layer4 on libavt as inside FullModel (R3DTrunk), then AdaptiveAvgPool3d((1,1,1)) + fc on the pooled
-    fp32 features.  Forward only, as everywhere in this build (FullModel detaches the video trunk)."""
+    fp32 features.  with_backward (a standalone module after ``enable_backward()``): the dgrad operands are packed
+    too, ``forward(..., tape=True)`` keeps the backward's tape and ``backward`` fills the flat gradient of every
+    vidnet parameter; inside FullModel the trunk stays forward-only (the reference detaches it, model.py:14)."""
 
-    def __init__(self, flat: FlatStore, prefix: str, max_pool: bool = False):
+    def __init__(self, flat: FlatStore, prefix: str, max_pool: bool = False, with_backward: bool = False):
         self._prefix = prefix
         self._max_pool = max_pool
+        self.with_backward = with_backward
+        self.packs3d_t: Dict[str, torch.Tensor] = {}
         super().__init__(flat)
         self.concurrent = False
         self.store = _TubeStore(self)
@@ -353,8 +489,8 @@ class R3DEngine(AVEngine):
     def pack_weights(self):
         _pack3d(self)
 
-    def forward(self, video: torch.Tensor, training: bool) -> torch.Tensor:
-        """video fp32 [b,3,t,H,W] -> fc logits [b, n_classes] fp32."""
+    def forward(self, video: torch.Tensor, training: bool, tape: bool = False):
+        """video fp32 [b,3,t,H,W] -> fc logits [b, n_classes] fp32 (tape=True: (logits, tape) for ``backward``)."""
         if not video.is_cuda:
             raise RuntimeError("avt: inputs must be on the GPU (no CPU path)")
         if video.dim() != 5:
@@ -362,8 +498,35 @@ class R3DEngine(AVEngine):
         self.pack_weights()
         if training and self._nbt_idx.numel():
             self.flat.nbt.index_add_(0, self._nbt_idx, torch.ones_like(self._nbt_idx))
-        v = self.vid.forward(video, self.store, training)  # [(b t), h, w, 512] bf16
         b = video.shape[0]
-        feat = v.view(b, -1, v.shape[-1]).float().mean(1)  # AdaptiveAvgPool3d((1,1,1)) + flatten
         w, bias = self.flat.raw(self._prefix + "fc.weight"), self.flat.raw(self._prefix + "fc.bias")
+        if tape:
+            if not self.with_backward:
+                raise RuntimeError("avt: this R3D engine was built forward-only")
+            v, tp = self.vid.forward(video, self.store, training, tape=True)
+            feat = v.view(b, -1, v.shape[-1]).float().mean(1)
+            tp.update(v_shape=tuple(v.shape), feat=feat)
+            return torch.addmm(bias, feat, w.t()), tp
+        v = self.vid.forward(video, self.store, training)  # [(b t), h, w, 512] bf16
+        feat = v.view(b, -1, v.shape[-1]).float().mean(1)  # AdaptiveAvgPool3d((1,1,1)) + flatten
         return torch.addmm(bias, feat, w.t())  # nn.Linear (resnet3D.py:212)
+
+    def backward(self, tape, glogits: torch.Tensor, gflat: torch.Tensor) -> None:
+        """d(loss)/d(logits) [b, n_classes] -> the gradient of every vidnet parameter, accumulated into the flat
+        buffer gflat[:n_train] (zeroed by the caller).  The fc and AdaptiveAvgPool3d backward run in torch on the
+        [b, 512] features (a few kilobytes); the rest is R3DTrunk.backward."""
+        grads = self.flat.grad_views(gflat)
+        glogits = glogits.contiguous().float()
+        w = self.flat.raw(self._prefix + "fc.weight")
+        grads[self._prefix + "fc.weight"].addmm_(glogits.t(), tape["feat"])
+        grads[self._prefix + "fc.bias"].add_(glogits.sum(0))
+        n, h, wd, C = tape["v_shape"]
+        b = glogits.shape[0]
+        per = (n // b) * h * wd  # positions the average pool spans per clip
+        gfeat = torch.mm(glogits, w) / per
+        g = gfeat.to(torch.bfloat16).view(b, 1, C).expand(b, per, C).contiguous().view(n, h, wd, C)
+        self.store.grads = grads
+        try:
+            self.vid.backward(tape, g, self.store)
+        finally:
+            self.store.grads = None

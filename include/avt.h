@@ -194,6 +194,41 @@ int avt_pack_conv3d_weights_batched(const void* descs, int n, int max_k, int max
  * [N][(T-1)/2+1][(H-1)/2+1][(W-1)/2+1][C] (the winning input's bits; NaN propagates) */
 int avt_maxpool3d_fwd(const void* x, void* y, int N, int T, int H, int W, int C, void* stream);
 
+/* ---- Conv3d backward: the trainable R3D-18 trunk (autograd through models/resnet3D.py:14-20 conv3x3x3 / conv1x1x1 in
+ * BasicBlock.forward 45-61, the stem's MaxPool3d :129 and ResNet.forward 197-213).  Conventions of the forward
+ * entries: NDHWC bf16 activations, temporal stride 1, spatial stride 1 or 2, Cp % 32 == 0, K % 64 == 0, fp32 sums. */
+/* w fp32 OIDHW [K][C][KT][R][S] -> bf16 out[c][(KT-1-kt, R-1-r, S-1-s, k)]: avt_pack_conv3d_weight's fold-0 layout
+ * with K and C swapped and the taps reversed -- the weight operand of avt_conv3d_dgrad (the weight transposition of
+ * autograd's conv3d input gradient, resnet3D.py:14-20).  K % 64 == 0, at most 64 taps. */
+int avt_pack_conv3d_weight_dgrad(const float* w, void* out, int K, int C, int KT, int R, int S, void* stream);
+/* ... for a device table of n avt_pack3d_desc_bytes() records in one launch (record.out = that conv's dgrad operand
+ * [C][T*K]; max_blocks = the largest C*K/64): the trunk's weights change every step once it trains */
+int avt_pack_conv3d_weights_dgrad_batched(const void* descs, int n, int max_blocks, void* stream);
+/* dx[N,T,H,W,C] = conv3d_input(dy[N,T',P,Q,K], wt) (+ add[N,T,H,W,C] if add != NULL; add may alias dx): the input
+ * gradient of conv3x3x3 (resnet3D.py:14-20; BasicBlock.forward 45-61, `out += residual` :58 entering as `add`).
+ * Stride 1 runs avt_conv3d_fwd's kernels (its three-patch halo form included) on dy with pad' = k-1-pad; stride 2
+ * walks, per (h%2, w%2) parity class of dx, only the class's spatial taps times the KT temporal taps.  Frames outside
+ * a clip contribute zero.  C % 64 == 0, K % 32 == 0. */
+int avt_conv3d_dgrad(const void* dy, const void* wt, void* dx, const void* add, int N, int T, int H, int W, int C, int K,
+                     int KT, int R, int S, int stride, int pad_t, int pad, void* stream);
+/* dw[K][Cp][KT][R][S] (fp32 OIDHW, the Parameter's layout) += conv3d_weight(x[N,T,H,W,Cp], dy[N,T,P,Q,K]): the weight
+ * gradient of conv3x3x3 (resnet3D.py:14-20).  Temporal 'same' padding (T' == T).  Every split-K partial goes through
+ * the fp32 slab in `workspace` (>= avt_conv3d_wgrad_workspace(...) bytes, 16-byte aligned, any contents) and is summed
+ * in split order: bitwise reproducible; there is no atomic path -- a NULL or short workspace is AVT_EINVAL. */
+size_t avt_conv3d_wgrad_workspace(int N, int T, int H, int W, int Cp, int K, int KT, int R, int S, int stride, int pad_t,
+                                  int pad);
+int avt_conv3d_wgrad(const void* x, const void* dy, float* dw, int N, int T, int H, int W, int Cp, int K, int KT, int R,
+                     int S, int stride, int pad_t, int pad, void* workspace, size_t ws_bytes, void* stream);
+/* gx[N,T,H,W,C] = backward of avt_maxpool3d_fwd (nn.MaxPool3d(3, 2, 1), resnet3D.py:129, 200-201) under
+ * gy[N,To,Ho,Wo,C]: each input voxel sums the gy of the at most 8 windows it wins (no atomics); a window's winner is
+ * its first maximum in (t, h, w) scan order, recomputed from x (torch's CPU max_pool3d choice).  y is not read. */
+int avt_maxpool3d_bwd(const void* gy, const void* x, const void* y, void* gx, int N, int T, int H, int W, int C,
+                      void* stream);
+/* R3D stem Conv3d(3,64,(7,7,7),s(1,2,2),p3) weight gradient (resnet3D.py:122-127): dwf fp32 [K][R][S][32] is
+ * avt_conv2d_wgrad's result over the folded input of avt_video_stem_im2col (Cp = Creal = 32, with its workspace:
+ * deterministic); dw[k][c][kt][r][s] (fp32 OIDHW [K][C][KT][R][S]) += dwf[k][r][s][kt*4 + c] */
+int avt_stem3d_wgrad_unfold(const float* dwf, float* dw, int K, int C, int KT, int R, int S, void* stream);
+
 /* tube-step audio de-duplication: out[b*rep+k][:] = in[b][:]  /  out[b][:] = sum_k in[b*rep+k][:] */
 int avt_repeat_rows_f32(const float* in, float* out, int B, int rep, int C, void* stream);
 int avt_sum_rep_rows_f32(const float* in, float* out, int B, int rep, int C, void* stream);

@@ -1,6 +1,8 @@
 """Per-shape microbenchmark of avt_conv3d_fwd (the tube step's R3D-18 3x3x3 convs, b clips of t frames)
 across the tap-gather NT kernel's tile configs (avt_set_nt64_config / avt_set_nt128_config).  Prints TFLOP/s.
-usage: python tools/conv3d_bench.py [--clips 8] [--frames 16] [--nt64 1,0,2,...] [--nt128 -1,1,2,...]"""
+--mode bwd: the backward of the same seven shapes instead -- avt_conv3d_dgrad next to the forward of the same shape
+from the same run (a stride-1 dgrad runs the forward's kernel, so the two should be close) and avt_conv3d_wgrad.
+usage: python tools/conv3d_bench.py [--clips 8] [--frames 16] [--nt64 1,0,2,...] [--nt128 -1,1,2,...] [--mode fwd|bwd]"""
 import argparse
 import os
 import sys
@@ -10,7 +12,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import avtubes  # noqa: E402,F401
-from avt_amd._lib import call  # noqa: E402
+from avt_amd._lib import call, query  # noqa: E402
 from conv_bench import P, S, timeit  # noqa: E402
 
 # (name, H, W, C, K, stride): the R3D-18 trunk at 224x224 frames (no max-pool; tube.py)
@@ -25,8 +27,36 @@ SHAPES = [
 ]
 
 
+def bench_bwd(b, T, dev):
+    """fwd / dgrad / wgrad TFLOP/s per R3D-18 shape (default knobs), one line each."""
+    for name, H, W, C, K, st in SHAPES:
+        Ho, Wo = (H + 2 - 3) // st + 1, (W + 2 - 3) // st + 1
+        x = torch.randn(b, T, H, W, C, device=dev).relu().to(torch.bfloat16)
+        dy = torch.randn(b, T, Ho, Wo, K, device=dev).to(torch.bfloat16)
+        w = torch.randn(K, C, 3, 3, 3, device=dev) * 0.05
+        wf = torch.empty(K, 27 * C, device=dev, dtype=torch.bfloat16)
+        wt = torch.empty(C, 27 * K, device=dev, dtype=torch.bfloat16)
+        call("avt_pack_conv3d_weight", P(w), P(wf), K, C, 3, 3, 3, 0, S())
+        call("avt_pack_conv3d_weight_dgrad", P(w), P(wt), K, C, 3, 3, 3, S())
+        y = torch.empty(b * T, Ho, Wo, K, device=dev, dtype=torch.bfloat16)
+        dx = torch.empty(b * T, H, W, C, device=dev, dtype=torch.bfloat16)
+        dw = torch.zeros(K, C, 3, 3, 3, device=dev)
+        wsb = int(query("avt_conv3d_wgrad_workspace", b, T, H, W, C, K, 3, 3, 3, st, 1, 1))
+        ws = torch.empty(wsb, device=dev, dtype=torch.uint8)
+        flops = 2.0 * y.numel() * 27 * C
+        f = timeit(lambda: call("avt_conv3d_fwd", P(x), P(wf), P(y), None, b, T, H, W, C, K, 3, 3, 3, st, 1, 1, S()))
+        d = timeit(lambda: call("avt_conv3d_dgrad", P(dy), P(wt), P(dx), None, b, T, H, W, C, K, 3, 3, 3, st, 1, 1,
+                                S()))
+        g = timeit(lambda: call("avt_conv3d_wgrad", P(x), P(dy), P(dw), b, T, H, W, C, K, 3, 3, 3, st, 1, 1, P(ws),
+                                wsb, S()))
+        print(f"{name:10s} M={b * T * Ho * Wo:8d} N={K:4d} K={27 * C:5d} | fwd {flops / f / 1e9:5.0f} TF/s "
+              f"({f * 1e3:7.1f} us) | dgrad {flops / d / 1e9:5.0f} TF/s ({d * 1e3:7.1f} us) | wgrad "
+              f"{flops / g / 1e9:5.0f} TF/s ({g * 1e3:7.1f} us, slab {wsb / 2 ** 20:.1f} MiB)", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--mode", default="fwd", choices=["fwd", "bwd"])
     ap.add_argument("--clips", type=int, default=8)
     ap.add_argument("--frames", type=int, default=16)
     ap.add_argument("--nt64", default="-1")
@@ -41,6 +71,9 @@ def main():
     for _ in range(50):
         warm @ warm
     torch.cuda.synchronize()
+    if args.mode == "bwd":
+        bench_bwd(b, T, dev)
+        return
     for name, H, W, C, K, st in SHAPES:
         Ho, Wo = (H + 2 - 3) // st + 1, (W + 2 - 3) // st + 1
         x = torch.randn(b, T, H, W, C, device=dev).relu().to(torch.bfloat16)
