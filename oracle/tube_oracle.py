@@ -104,6 +104,12 @@ def make_video(b: int, t: int = 16, size: int = 224, seed: int = 3) -> torch.Ten
     return torch.from_numpy(rng.standard_normal((b, 3, t, size, size), dtype=np.float32))
 
 
+def make_glogits(b: int, n_classes: int = 1039, seed: int = 29) -> torch.Tensor:
+    """A fixed dense upstream gradient [b, n_classes] (standard normal, fp64) of the trunk's fc logits: the loss of the
+    forced-tape gradient checks is (logits * glogits).sum()."""
+    return torch.randn(b, n_classes, generator=torch.Generator().manual_seed(seed), dtype=torch.float64)
+
+
 def repeat_spectrogram(spec: torch.Tensor, t: int) -> torch.Tensor:
     """train_3D.py:128-130: [b,1,F,T] -> repeat t -> '(b t) 1 F T'."""
     b = spec.shape[0]
@@ -135,6 +141,101 @@ def r3d18_forward(sd, prefix: str, x: torch.Tensor, training: bool = True, max_p
                 res = _bn3(res, sd, p + "downsample.1", training)
             x = F.relu(out + res)
     return x
+
+
+def _max_pool3d_last(x: torch.Tensor) -> torch.Tensor:
+    """MaxPool3d(3, 2, 1) whose gradient goes to the LAST maximum of a window in scan order (torch's own, and the
+    trunk's, go to the first): r3d18_forward_forced's "pool_last" fault."""
+    xp = F.pad(x, (1, 1, 1, 1, 1, 1), value=float("-inf"))
+    To, Ho, Wo = [(n - 1) // 2 + 1 for n in x.shape[2:]]
+    taps = torch.stack([xp[:, :, dt:dt + 2 * To:2, dh:dh + 2 * Ho:2, dw:dw + 2 * Wo:2]
+                        for dt in range(3) for dh in range(3) for dw in range(3)])
+    idx = 26 - taps.detach().flip(0).argmax(0, keepdim=True)  # argmax returns the first of equal maxima
+    return taps.gather(0, idx)[0]
+
+
+FORCED_FAULTS = ("drop_identity", "drop_downsample", "mask_c2", "pool_last")
+
+
+def r3d18_forward_forced(sd, prefix: str, x: torch.Tensor, tape: dict, max_pool: bool = False, grad_round=None,
+                         fault: str = None) -> torch.Tensor:
+    """r3d18_forward's graph in train mode, "teacher-forced" onto a recorded forward state: for a fixed forward state
+    the backward is a linear map of the upstream gradient, so autograd through this function is the reference of a
+    trunk's backward on that trunk's OWN forward (tape: c0, h0, blocks[i] = c1, h1, c2, cd, out, NCDHW: the stem's
+    conv output and ReLU output, each block's conv outputs, inner ReLU output and block output), with the forward's rounding noise (flipped ReLU masks, shifted batch statistics)
+    taken out of the comparison.
+      * every conv output is set to the tape's value, c + (c_tape - c).detach(); the batch statistics are those of the
+        forced conv outputs (no running statistics are read or written);
+      * every ReLU output is z * [stored > 0] (h0, h1, out: the recorded masks), then set to the stored value;
+      * the max-pool acts on the forced h0 (torch routes a window's gradient to its first maximum);
+      * sd: the weights to differentiate (the caller rounds the conv weights to bf16); x is rounded to bf16 here.
+    grad_round: a function applied (as an autograd hook) to the gradient of every activation the trunk's backward
+    stores -- c0, h0, the max-pool output, c1, h1, c2, cd, out -- e.g. a rounding to bf16: the yardstick of a correct
+    implementation with those storage formats.  fault (tests only; FORCED_FAULTS): a deliberately mis-wired graph --
+    "drop_identity" layer1.1's identity branch passes no gradient, "drop_downsample" layer2.0's downsample branch
+    passes none, "mask_c2" the block-output masks are [c2 > 0], "pool_last" the max-pool gradient goes to a window's
+    last maximum."""
+    assert fault is None or fault in FORCED_FAULTS, fault
+    dt = sd[prefix + "conv1.weight"].dtype
+
+    def keep(t):
+        if grad_round is not None and t.requires_grad:
+            t.register_hook(grad_round)
+        return t
+
+    def force(z, v):
+        return keep(z + (v.to(dt) - z).detach())
+
+    def bn(c, name):
+        return F.batch_norm(c, None, None, sd[name + ".weight"], sd[name + ".bias"], True, 0.0, 1e-5)
+
+    x = x.to(torch.bfloat16).to(dt)
+    c = force(F.conv3d(x, sd[prefix + "conv1.weight"], stride=(1, 2, 2), padding=(3, 3, 3)), tape["c0"])
+    x = force(bn(c, prefix + "bn1") * (tape["h0"] > 0), tape["h0"])
+    if max_pool:
+        x = keep(_max_pool3d_last(x) if fault == "pool_last" else F.max_pool3d(x, kernel_size=3, stride=2, padding=1))
+    blocks = iter(tape["blocks"])
+    for li, (planes, stride) in enumerate(R3D_STAGES, start=1):
+        for bi in range(2):
+            s = stride if bi == 0 else 1
+            p = f"{prefix}layer{li}.{bi}."
+            tb = next(blocks)
+            c1 = force(F.conv3d(x, sd[p + "conv1.weight"], stride=(1, s, s), padding=1), tb["c1"])
+            h1 = force(bn(c1, p + "bn1") * (tb["h1"] > 0), tb["h1"])
+            c2 = force(F.conv3d(h1, sd[p + "conv2.weight"], stride=1, padding=1), tb["c2"])
+            z = bn(c2, p + "bn2")
+            if (p + "downsample.0.weight") in sd:
+                cd = force(F.conv3d(x, sd[p + "downsample.0.weight"], stride=(1, s, s)), tb["cd"])
+                res = bn(cd, p + "downsample.1")
+                if fault == "drop_downsample" and (li, bi) == (2, 0):
+                    res = res.detach()
+            else:
+                res = x.detach() if fault == "drop_identity" and (li, bi) == (1, 1) else x
+            mask = (tb["c2"] > 0) if fault == "mask_c2" else (tb["out"] > 0)
+            x = force((z + res) * mask, tb["out"])
+    return x
+
+
+def r3d18_forced_grads(sd, video: torch.Tensor, tape: dict, glogits: torch.Tensor, max_pool: bool,
+                       round_grads: bool = False, fault: str = None, prefix: str = "vidnet."):
+    """{name without prefix: fp64 gradient} of (fc(avgpool(r3d18_forward_forced(...))) * glogits).sum() on the CPU for
+    every trunk parameter: conv weights are the bf16-rounded parameters in fp64 (the gradient is taken at them), BN
+    and fc parameters, the average pool and the fc stay fp64.  round_grads: every stored activation gradient is
+    rounded to bf16 (the weight gradients stay full sums)."""
+    names = [k for k, v in sd.items() if k.startswith(prefix) and v.is_floating_point()
+             and not k.endswith(("running_mean", "running_var"))]
+    s = {}
+    for n in names:
+        v = sd[n].detach()
+        v = v.to(torch.bfloat16) if v.dim() == 5 else v
+        s[n] = v.to(torch.float64).clone().requires_grad_(True)
+    rnd = (lambda g: g.to(torch.bfloat16).to(g.dtype)) if round_grads else None
+    tape64 = {k: v.double() for k, v in tape.items() if k != "blocks"}
+    tape64["blocks"] = [{k: v.double() for k, v in tb.items()} for tb in tape["blocks"]]
+    feat = r3d18_forward_forced(s, prefix, video, tape64, max_pool=max_pool, grad_round=rnd, fault=fault)
+    logits = F.linear(feat.mean(dim=(2, 3, 4)), s[prefix + "fc.weight"], s[prefix + "fc.bias"])
+    (logits * glogits.double()).sum().backward()
+    return {n[len(prefix):]: s[n].grad for n in names}
 
 
 def fullmodel_forward(sd, audio: torch.Tensor, video: torch.Tensor, training: bool = True):

@@ -16,6 +16,26 @@ def _sample(t, n=256):
     return f[::max(1, f.numel() // n)][:n].double().cpu().numpy()
 
 
+def rule_full(v, ref, yard):
+    """check_grads' three rules on whole tensors (v: the gradient under test, ref: the fp64 reference, yard: the
+    yardstick): (violations, e, e_ref, bound ratio) -- violations lists (kind, value, yardstick's value) for an error
+    vector > max(5e-2, 3 e_ref), a cosine < min(0.999, 1 - 3 (1 - cos_ref)), a norm deviation > max(5e-2, 3 d_ref,
+    e_ref); the ratio is e over its bound."""
+    v, ref, yard = (np.asarray(t, np.float64).ravel() for t in (v, ref, yard))
+    nr = max(np.linalg.norm(ref), 1e-300)
+    e, e_ref = float(np.linalg.norm(v - ref) / nr), float(np.linalg.norm(yard - ref) / nr)
+    c, c_ref = _cos(v, ref), _cos(yard, ref)
+    d, d_ref = abs(float(np.linalg.norm(v)) / nr - 1), abs(float(np.linalg.norm(yard)) / nr - 1)
+    bad = []
+    if not e <= max(5e-2, 3 * e_ref):
+        bad.append(("error", round(e, 4), round(e_ref, 4)))
+    if not c >= min(0.999, 1 - 3 * (1 - c_ref)):
+        bad.append(("cosine", round(c, 5), round(c_ref, 5)))
+    if not d <= max(5e-2, 3 * d_ref, e_ref):
+        bad.append(("norm", round(d, 4), round(d_ref, 4)))
+    return bad, e, e_ref, e / max(5e-2, 3 * e_ref)
+
+
 def check_grads(g, grads, tag=""):
     """Every parameter's gradient against the fp64 reference, each bounded by ITS OWN yardstick -- the
     reference's trunks under bf16 autocast at the same size (stored by gen_golden_full.py).  On a

@@ -57,7 +57,30 @@ CASES = [
     (1, 2, 3, 3, 512, 512, 1),
     (3, 5, 28, 28, 128, 128, 1),  # clip ends inside a tile
     (1, 16, 14, 14, 256, 512, 2),
+    # the wgrad's frames of fewer than 32 positions (several frames per k-tile), as the stock trunk's layer4 has them
+    (8, 5, 4, 4, 256, 512, 1),    # 640 positions = 20 k-tiles, >= 2 splits; odd T: a clip end inside a k-tile
+    (8, 4, 7, 7, 256, 512, 2),    # stride 2 into 4 x 4 frames, 16 k-tiles, >= 2 splits
+    (4, 3, 4, 4, 512, 512, 1),    # several k-tiles, one split
+    (20, 4, 2, 1, 64, 128, 1),    # Q = 1: a k-tile steps 32 rows and no columns; P*Q = 2
+    (5, 3, 1, 1, 64, 64, 1),      # one position per frame
+    (2, 3, 4, 8, 64, 64, 1),      # P*Q = 32: the first size off that branch
+    (2, 3, 3, 11, 64, 64, 1),     # P*Q = 33
+    (2, 3, 1, 31, 64, 64, 1),     # P*Q = 31: the last size on it
+    # stride-2 dgrad parity classes
+    (2, 3, 8, 7, 64, 128, 2),     # even H, odd W
+    (3, 2, 1, 5, 64, 128, 2),     # H = 1: the ph = 1 classes are empty
+    (3, 2, 5, 1, 64, 128, 2),     # W = 1: the pw = 1 classes are empty
+    # stride-1 dgrad on every patch form of the forward's launch path, either side of each switch in width
+    (1, 2, 5, 39, 128, 128, 1),   # the last width on the 336-row patch (C % 128 == 0)
+    (1, 2, 5, 40, 128, 128, 1),   # the first on the two-weight-stage form
+    (1, 2, 5, 79, 128, 128, 1),   # its last
+    (1, 2, 5, 80, 128, 128, 1),   # the tap gather
+    (1, 2, 56, 56, 128, 128, 1),  # layer2's width, 416-row patch
+    (1, 2, 5, 115, 64, 64, 1),    # the last width on the 488-row patch (C = 64)
+    (1, 2, 5, 116, 64, 64, 1),    # the tap gather
+    (1, 2, 20, 112, 64, 64, 1),   # layer1's width, 488-row patch
 ]
+SPLIT_CASES = CASES[7:9]  # must reach the wgrad's split-K (asserted from the workspace size)
 
 
 def _pack_dgrad(w):
@@ -113,25 +136,32 @@ def _dgrad(dy, wt, dx, add, case):
 
 @pytest.mark.parametrize("case", CASES)
 def test_conv3d_dgrad(case):
-    """avt_conv3d_dgrad vs torch.nn.grad.conv3d_input in fp64 on the same bf16 operands: plain, + add, add aliasing dx."""
+    """avt_conv3d_dgrad vs torch.nn.grad.conv3d_input in fp64 on the same bf16 operands: plain, + add, add aliasing dx.
+    A stride-1 case runs the forward's launch path: on its default form for the shape (avt_set_halo3d(-1)) and on the
+    tap gather (0)."""
     N, T, H, W, C, K, st = case
     d = _case_data(case)
     wt = _pack_dgrad(d["w"].to(DEV))
     dy, add = d["dy"].to(DEV), d["add"].to(DEV)
-    dx = torch.full((N, T, H, W, C), float("nan"), device=DEV, dtype=torch.bfloat16)
-    _dgrad(dy, wt, dx, None, case)
-    e0 = rel_err(dx, d["dx"])
-    dx1 = torch.full_like(dx, float("nan"))
-    _dgrad(dy, wt, dx1, add, case)
     ref_add = d["dx"] + d["add"].double()
-    e1 = rel_err(dx1, ref_add)
-    dx2 = add.clone()
-    _dgrad(dy, wt, dx2, dx2, case)
-    torch.cuda.synchronize()
-    print(f"{case}: dgrad rel err {e0:.3e}, +add {e1:.3e}")
-    assert e0 < 8e-3, e0
-    assert e1 < 8e-3, e1
-    assert torch.equal(dx2, dx1)  # in place: the same bits as out of place
+    try:
+        for halo3d in ((-1, 0) if st == 1 else (-1,)):
+            call("avt_set_halo3d", halo3d)
+            dx = torch.full((N, T, H, W, C), float("nan"), device=DEV, dtype=torch.bfloat16)
+            _dgrad(dy, wt, dx, None, case)
+            e0 = rel_err(dx, d["dx"])
+            dx1 = torch.full_like(dx, float("nan"))
+            _dgrad(dy, wt, dx1, add, case)
+            e1 = rel_err(dx1, ref_add)
+            dx2 = add.clone()
+            _dgrad(dy, wt, dx2, dx2, case)
+            torch.cuda.synchronize()
+            print(f"{case} halo3d={halo3d}: dgrad rel err {e0:.3e}, +add {e1:.3e}")
+            assert e0 < 8e-3, (halo3d, e0)
+            assert e1 < 8e-3, (halo3d, e1)
+            assert torch.equal(dx2, dx1), halo3d  # in place: the same bits as out of place
+    finally:
+        call("avt_set_halo3d", -1)
 
 
 def _wgrad(x, dy, dw, case, ws="auto"):
@@ -150,6 +180,10 @@ def test_conv3d_wgrad(case):
     a NULL workspace is an error."""
     N, T, H, W, C, K, st = case
     d = _case_data(case)
+    if case in SPLIT_CASES:  # slab bytes = splits * K * Ng * 4, Ng = 27 C rounded up to 128
+        wsb = int(query("avt_conv3d_wgrad_workspace", N, T, H, W, C, K, 3, 3, 3, st, 1, 1))
+        Ng = (27 * C + 127) // 128 * 128
+        assert wsb % (K * Ng * 4) == 0 and wsb // (K * Ng * 4) >= 2, (wsb, K, Ng)
     x, dy = d["x"].to(DEV), d["dy"].to(DEV)
     dw = torch.full((K, C, 3, 3, 3), 0.25, device=DEV)
     dw2 = dw.clone()

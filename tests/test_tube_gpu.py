@@ -66,6 +66,17 @@ CONV3D_CASES = [
     (2, 3, 112, 112, 64, 64, 1),
     (3, 2, 21, 30, 64, 64, 1),
     (1, 5, 56, 56, 128, 64, 1),
+    # the widths at which halo3d_launch changes its patch form, either side: 39 | 40 (336 rows | kHaloPR rows), 79 | 80
+    # (N % 128 == 0: the halo form | the tap gather), 115 | 116 (N = 64: 488 rows | the tap gather)
+    (1, 2, 5, 39, 128, 128, 1),
+    (1, 2, 5, 40, 128, 128, 1),
+    (1, 2, 5, 79, 128, 128, 1),
+    (1, 2, 5, 80, 128, 128, 1),
+    (1, 2, 5, 115, 64, 64, 1),
+    (1, 2, 5, 116, 64, 64, 1),
+    # layer4's frames of the stock trunk: 4 x 4 positions over many clips, and one-column frames
+    (8, 5, 4, 4, 256, 512, 1),
+    (20, 4, 2, 1, 64, 128, 1),
 ]
 
 
