@@ -1016,13 +1016,19 @@ def test_pack_batched_matches_single():
 
 
 def test_adam_matches_torch():
+    """avt_adam_step (host scalars) over three steps: the update as a whole, and every element of p, exp_avg and
+    exp_avg_sq after every step against AdamRef on the fp32 hyper-parameters the entry receives, bounded by 3 x
+    the error of torch.optim.Adam in fp32 on the CPU (tests/adamcheck.py)."""
     import avenet_oracle as orc
+    from adamcheck import AdamPair, check_elementwise
 
     g = torch.Generator().manual_seed(23)
     n = 1001
     p0 = torch.randn(n, generator=g)
     opt = orc.AdamRef(lr=1e-3, weight_decay=1e-4)
     pr = {"p": p0.clone().double()}
+    g2 = torch.Generator().manual_seed(24)  # the rest of the 4096 elements the yardstick is measured on
+    pair = AdamPair(torch.cat([p0, torch.randn(4096 - n, generator=g2)]), (1e-3, 0.9, 0.999, 1e-8, 1e-4))
     pd = p0.clone().to(DEV)
     m = torch.zeros(n, device=DEV)
     v = torch.zeros(n, device=DEV)
@@ -1030,6 +1036,9 @@ def test_adam_matches_torch():
         gr = torch.randn(n, generator=g)
         opt.step(pr, {"p": gr.double()})
         call("avt_adam_step", P(pd), P(D(gr)), P(m), P(v), n, 1.0, 1e-3, 0.9, 0.999, 1e-8, 1e-4, t, S())
+        ref, yard, unit = pair.step(torch.cat([gr, torch.randn(4096 - n, generator=g2)]))
+        torch.cuda.synchronize()
+        check_elementwise(f"avt_adam_step t={t}", {"p": pd, "m": m, "v": v}, ref, yard, unit, n)
     torch.cuda.synchronize()
     assert rel_err(pd - p0.to(DEV), pr["p"] - p0.double()) < 1e-4
 
