@@ -108,6 +108,11 @@ SIGNATURES = {
     "avt_conv3d_wgrad": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _Z, _P]),
     "avt_maxpool3d_bwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "avt_stem3d_wgrad_unfold": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
+    "avt_set_video_stem_dgrad": (_I, [_I]),
+    "avt_video_stem_dgrad_pack_bytes": (_Z, []),
+    "avt_pack_video_stem_dgrad": (_I, [_P, _P, _P]),
+    "avt_video_stem_dgrad": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "avt_bn_eval_bwd": (_I, [_P, _P, _P, _P, ctypes.POINTER(BnBwdTarget), ctypes.POINTER(BnBwdTarget), _P, _L, _I, _P]),
     "avt_pack3d_desc_bytes": (_Z, []),
     "avt_pack_conv3d_weights_batched": (_I, [_P, _I, _I, _I, _P]),
     "avt_pack_conv3d_weight": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),

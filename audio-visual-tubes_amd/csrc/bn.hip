@@ -720,9 +720,152 @@ static void bn_bwd_reduce_launch(const bf16_t* g, const bf16_t* y, const float* 
                      rows, C, (int)rpb);
 }
 
+// ---------------------------------------------------------------------------------------------
+// Eval-mode (running-statistics) BatchNorm backward.  With fixed statistics BN is a per-channel affine map, so the
+// mean terms of the train-mode rule vanish and one pass does everything: g' = g * mask, gc = gamma*invstd*g' (and
+// gc2 of a second BN fed by the same g': a first block's bn2 + downsample.1), and -- only for a BN whose dgamma or
+// dbeta is wanted -- the block's (sum g', sum g'*xhat) into its own slot of the fixed-order workspace, xhat =
+// (xc - running_mean)*invstd.  Rows are dealt to blocks and threads as in bn_bwd_reduce_kernel.
+struct EvalBwdArgs {
+  const bf16_t* g;
+  const bf16_t* y;      // mask y > 0, or
+  const float* mscale;  // mask fma(xc, mscale, mshift) > 0 (xc of the first BN), or none
+  const float* mshift;
+  bf16_t* gmask_out;    // optional g'
+  const bf16_t* xc[2];
+  const float* mean[2];
+  const float* invstd[2];
+  const float* gamma[2];
+  bf16_t* gc[2];
+  double* acc[2];       // NULL: no parameter gradient of that BN, nothing is reduced
+  long long rows;
+  int C, rows_per_block;
+};
+
+template <bool TWO>
+__global__ __launch_bounds__(256) void bn_eval_bwd_kernel(EvalBwdArgs a) {
+  __shared__ float red[2048 * 2];
+  constexpr int NB = TWO ? 2 : 1;
+  const int C = a.C, cv = C / 8;
+  const int chunk = threadIdx.x % cv, r0 = threadIdx.x / cv, rstep = 256 / cv;
+  const int c0 = chunk * 8;
+  float mu[NB][8], is[NB][8], gi[NB][8], s1[8], s2[NB][8];
+#pragma unroll
+  for (int b = 0; b < NB; ++b)
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      mu[b][e] = a.mean[b][c0 + e];
+      is[b][e] = a.invstd[b][c0 + e];
+      gi[b][e] = a.gamma[b][c0 + e] * is[b][e];
+      s2[b][e] = 0.f;
+    }
+#pragma unroll
+  for (int e = 0; e < 8; ++e) s1[e] = 0.f;
+  const long long rbeg = (long long)blockIdx.x * a.rows_per_block;
+  const long long rend = min(a.rows, rbeg + a.rows_per_block);
+  for (long long r = rbeg + r0; r < rend; r += rstep) {
+    const size_t off = (size_t)r * cv + chunk;
+    float gg[8], xx[8], o[8];
+    unpack8(reinterpret_cast<const u32x4*>(a.g)[off], gg);
+    unpack8(reinterpret_cast<const u32x4*>(a.xc[0])[off], xx);
+    relu_mask8(gg, xx, a.y, off, a.mscale, a.mshift, c0);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      s1[e] += gg[e];
+      s2[0][e] += gg[e] * (xx[e] - mu[0][e]) * is[0][e];
+      o[e] = gi[0][e] * gg[e];
+    }
+    reinterpret_cast<u32x4*>(a.gc[0])[off] = pack8(o);
+    if (a.gmask_out) reinterpret_cast<u32x4*>(a.gmask_out)[off] = pack8(gg);
+    if (TWO) {
+      unpack8(reinterpret_cast<const u32x4*>(a.xc[NB - 1])[off], xx);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        s2[NB - 1][e] += gg[e] * (xx[e] - mu[NB - 1][e]) * is[NB - 1][e];
+        o[e] = gi[NB - 1][e] * gg[e];
+      }
+      reinterpret_cast<u32x4*>(a.gc[NB - 1])[off] = pack8(o);
+    }
+  }
+#pragma unroll
+  for (int b = 0; b < NB; ++b) {
+    if (!a.acc[b]) continue;  // (uniform over the block)
+    __syncthreads();
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      red[(r0 * C + c0 + e) * 2] = s1[e];
+      red[(r0 * C + c0 + e) * 2 + 1] = s2[b][e];
+    }
+    __syncthreads();
+    bn_write_header(a.acc[b], gridDim.x, 0);
+    double* slot = bn_bwd_slots(a.acc[b], C) + (size_t)blockIdx.x * C * 2;  // this block's own slot
+    for (int c = threadIdx.x; c < C; c += blockDim.x) {
+      float p = 0.f, q = 0.f;
+      for (int k = 0; k < rstep; ++k) {
+        p += red[(k * C + c) * 2];
+        q += red[(k * C + c) * 2 + 1];
+      }
+      slot[2 * c] = (double)p;
+      slot[2 * c + 1] = (double)q;
+    }
+  }
+}
+
 }  // namespace avt
 
 using namespace avt;
+
+// Eval-mode BatchNorm backward (see bn_eval_bwd_kernel).  t1 (and t2, sharing g') as avt_bn_bwd_mask's targets with
+// mean = running_mean and invstd = rsqrt(running_var + eps); a target's workspace is read only when its dgamma or
+// dbeta is non-NULL.  Mask: y (y > 0) if given, else (mscale, mshift) on t1's xc if given, else none.
+extern "C" int avt_bn_eval_bwd(const void* g, const void* y, const float* mscale, const float* mshift,
+                               const avt_bn_bwd_target* t1, const avt_bn_bwd_target* t2, void* gmask_out,
+                               long long rows, int C, void* stream) {
+  AVT_REQUIRE(g && t1, "bn_eval_bwd: null pointer");
+  AVT_REQUIRE((mscale == nullptr) == (mshift == nullptr), "bn_eval_bwd: mscale/mshift must be both set or both null");
+  AVT_REQUIRE(C % 8 == 0 && C <= 2048 && 256 % (C / 8) == 0, "bn_eval_bwd: C=%d unsupported", C);
+  AVT_REQUIRE(rows > 0, "bn_eval_bwd: empty input");
+  const avt_bn_bwd_target* ts[2] = {t1, t2};
+  EvalBwdArgs a{};
+  a.g = (const bf16_t*)g;
+  a.y = (const bf16_t*)y;
+  a.mscale = y ? nullptr : mscale;
+  a.mshift = y ? nullptr : mshift;
+  a.gmask_out = (bf16_t*)gmask_out;
+  for (int k = 0; k < (t2 ? 2 : 1); ++k) {
+    const avt_bn_bwd_target* t = ts[k];
+    AVT_REQUIRE(t->xc && t->mean && t->invstd && t->gamma && t->gc, "bn_eval_bwd: null target pointer");
+    const bool wants = t->dgamma || t->dbeta;
+    AVT_REQUIRE(!wants || (t->workspace && ((uintptr_t)t->workspace & 7) == 0),
+                "bn_eval_bwd: dgamma/dbeta need an 8-byte aligned workspace");
+    a.xc[k] = (const bf16_t*)t->xc;
+    a.mean[k] = t->mean;
+    a.invstd[k] = t->invstd;
+    a.gamma[k] = t->gamma;
+    a.gc[k] = (bf16_t*)t->gc;
+    a.acc[k] = wants ? (double*)t->workspace : nullptr;
+  }
+  a.rows = rows;
+  a.C = C;
+  long long rpb = (rows + 511) / 512;  // ~2 blocks per CU of rows, as bn_bwd_reduce_launch
+  const int rstep = 256 / (C / 8);
+  rpb = ((rpb + rstep - 1) / rstep) * rstep;
+  if (rpb < rstep) rpb = rstep;
+  a.rows_per_block = (int)rpb;
+  const int nblk = (int)((rows + rpb - 1) / rpb);
+  hipStream_t st = (hipStream_t)stream;
+  if (t2)
+    hipLaunchKernelGGL(bn_eval_bwd_kernel<true>, dim3(nblk), dim3(256), 0, st, a);
+  else
+    hipLaunchKernelGGL(bn_eval_bwd_kernel<false>, dim3(nblk), dim3(256), 0, st, a);
+  for (int k = 0; k < (t2 ? 2 : 1); ++k) {
+    if (!a.acc[k]) continue;
+    float* k1 = (float*)(a.acc[k] + kBnHdr);  // (the train-mode rule's means: written, not used here)
+    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + kFinCB - 1) / kFinCB), dim3(kFinThreads), 0, st, a.acc[k], C,
+                       1.0 / (double)rows, ts[k]->dgamma, ts[k]->dbeta, k1, k1 + C);
+  }
+  return check_launch("bn_eval_bwd");
+}
 
 extern "C" size_t avt_bn_acc_doubles(long long rows, int C) {
   return rows < 0 || C <= 0 ? 0 : (size_t)kBnHdr + (size_t)bn_slot_cap(rows) * C * 3;

@@ -348,6 +348,220 @@ __global__ __launch_bounds__(256) void stem3d_wgrad_unfold_kernel(const float* _
   }
 }
 
+// ---- input gradient of the R3D stem Conv3d(3, 64, (7,7,7), stride (1,2,2), pad 3) (resnet3D.py:122-127) ----
+//   gx[n][c][tau][h][w] = sum_{kt, r, s, k} gy[n][tau - kt + 3][(h + 3 - r) / 2][(w + 3 - s) / 2][k] * w[k][c][kt][r][s]
+// over the frames inside the clip and the (r, s) of the voxel's (h % 2, w % 2) parity class whose output position
+// falls inside the P x Q map: 3 or 4 rows times 3 or 4 columns of the 7 x 7.  Both forms launch one block range per
+// class (the classes with the most taps first), blockIdx.y = the clip: a block never spans two clips.
+struct VsdArgs {
+  const bf16_t* gy;  // [N][T][P][Q][64]
+  const float* w;    // form 0: fp32 OIDHW [64][3][7][7][7]
+  const u32x4* wp;   // form 1: avt_pack_video_stem_dgrad's operand
+  float* gx;         // [N][3][T][H][W]
+  int T, H, W, P, Q;
+  int first[5];      // block range [first[i], first[i + 1]) of launch class i
+  int cls[4];        // its (h % 2) * 2 + (w % 2)
+};
+
+struct VsdClass {
+  int ph, pw, Wc, Mc, r0, s0, nr, ns, blk;
+};
+
+__device__ __forceinline__ VsdClass vsd_class(const VsdArgs& a) {
+  int ci = 0;
+  while (ci < 3 && (int)blockIdx.x >= a.first[ci + 1]) ++ci;
+  VsdClass c;
+  c.ph = a.cls[ci] >> 1;
+  c.pw = a.cls[ci] & 1;
+  c.Wc = (a.W - c.pw + 1) / 2;
+  c.Mc = ((a.H - c.ph + 1) / 2) * c.Wc;
+  c.r0 = (c.ph + 1) & 1;  // the taps r with h + 3 - r even: r0, r0 + 2, ...
+  c.s0 = (c.pw + 1) & 1;
+  c.nr = 4 - c.r0;
+  c.ns = 4 - c.s0;
+  c.blk = (int)blockIdx.x - a.first[ci];
+  return c;
+}
+
+// Form 0, direct: one thread per voxel (n, tau, h, w) of the block's class; fp32 weights, one temporal tap's class
+// taps at a time in LDS ([tap][k][4]); fp32 sums in the fixed order (kt, r, s, k).  The 3-D form of
+// stem_dgrad_kernel (misc.hip).
+__global__ __launch_bounds__(256) void video_stem_dgrad_direct_kernel(VsdArgs a) {
+  __shared__ float ws[16 * 64 * 4];
+  const VsdClass c = vsd_class(a);
+  const int n = blockIdx.y;
+  const int idx = c.blk * 256 + (int)threadIdx.x;
+  const bool valid = idx < a.T * c.Mc;
+  const int tau = valid ? idx / c.Mc : 0, m = valid ? idx - tau * c.Mc : 0;
+  const int hc = m / c.Wc, h = 2 * hc + c.ph, x = 2 * (m - hc * c.Wc) + c.pw;
+  float acc[3] = {0.f, 0.f, 0.f};
+  for (int kt = 0; kt < 7; ++kt) {
+    __syncthreads();
+    for (int i = threadIdx.x; i < c.nr * c.ns * 256; i += 256) {
+      const int ch = i & 3, k = (i >> 2) & 63, tap = i >> 8;
+      const int r = c.r0 + 2 * (tap / c.ns), s = c.s0 + 2 * (tap % c.ns);
+      ws[i] = ch < 3 ? a.w[((((size_t)k * 3 + ch) * 7 + kt) * 7 + r) * 7 + s] : 0.f;
+    }
+    __syncthreads();
+    const int t = tau - kt + 3;
+    if (!valid || t < 0 || t >= a.T) continue;
+    const bf16_t* fr = a.gy + ((size_t)n * a.T + t) * a.P * a.Q * 64;
+    for (int ia = 0; ia < c.nr; ++ia) {
+      const int p = (h + 3 - (c.r0 + 2 * ia)) >> 1;
+      if (p < 0 || p >= a.P) continue;
+      for (int ib = 0; ib < c.ns; ++ib) {
+        const int q = (x + 3 - (c.s0 + 2 * ib)) >> 1;
+        if (q < 0 || q >= a.Q) continue;
+        const u32x4* row = reinterpret_cast<const u32x4*>(fr + ((size_t)p * a.Q + q) * 64);
+        const float* wt = ws + (ia * c.ns + ib) * 256;
+#pragma unroll 2
+        for (int k8 = 0; k8 < 8; ++k8) {
+          const u32x4 v = row[k8];
+          const unsigned* u = reinterpret_cast<const unsigned*>(&v);
+#pragma unroll
+          for (int e = 0; e < 8; ++e) {
+            const float g = bf2f((bf16_t)(e & 1 ? u[e >> 1] >> 16 : u[e >> 1] & 0xffff));
+            const float4 wk = *reinterpret_cast<const float4*>(wt + (k8 * 8 + e) * 4);
+            acc[0] += g * wk.x;
+            acc[1] += g * wk.y;
+            acc[2] += g * wk.z;
+          }
+        }
+      }
+    }
+  }
+  if (valid)
+    for (int ch = 0; ch < 3; ++ch) a.gx[((((size_t)n * 3 + ch) * a.T + tau) * a.H + h) * a.W + x] = acc[ch];
+}
+
+// Form 1, MFMA: the transpose of the forward's folded 2-D conv (the file comment).  Per frame t and class,
+//   gxf[j = kt*4 + c][pixel] = sum_{(r, s) of the class, k} Wf[j][(r, s, k)] * gy[n][t][p][q][k]
+// is a GEMM with 32 rows (21 of them real), 16/12/12/9 x 64 of K and the class's pixels as columns, on
+// v_mfma_f32_16x16x32_bf16 with the WEIGHTS as the A operand: lane l then holds, for pixel l & 15, the four channels c
+// of temporal tap kt = 4 * jtile + (l >> 4) -- one float4 of the fold-back
+//   gx[n][c][t + kt - 3] += gxf[kt*4 + c]
+// which is fused: a wave owns kVsdPT tiles of 16 class pixels (consecutive in the class's (h, w) raster) and walks
+// the clip's frames in order, adding each frame's eight float4 per lane into its private LDS ring of 8 frames
+// [tau & 7][pixel][4]; the seven (kt) lanes of a pixel hit seven different frames, so the adds are plain (no
+// atomics) and a voxel's sum runs in the fixed order kt = 6 .. 0.  Frame tau is complete after frame tau + 3 and is
+// stored then.  The class's bf16 weights (<= 16 taps x 4 KB of A fragments) stay in LDS for the whole block; the gy
+// fragments are 16-byte loads straight from global memory (8 channels of one output pixel per lane; the 2 x 2 taps
+// around a pixel re-read it from L1/L2).  No intermediate gxf reaches memory and nothing is rounded to bf16 after
+// the operands: fp32 accumulation throughout.
+constexpr int kVsdPT = 2, kVsdPix = kVsdPT * 16;
+constexpr int kVsdWBytes = 16 * 4096, kVsdLds = kVsdWBytes + 4 * 8 * kVsdPix * 16;
+
+__global__ __launch_bounds__(256) void video_stem_dgrad_mfma_kernel(VsdArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char vsd_smem[];
+  const VsdClass c = vsd_class(a);
+  const int n = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane >> 4;
+  u32x4* wl = reinterpret_cast<u32x4*>(vsd_smem);  // [tap][k half][j tile][lane]
+  float4* ring = reinterpret_cast<float4*>(vsd_smem + kVsdWBytes) + wave * 8 * kVsdPix;
+  for (int i = threadIdx.x; i < c.nr * c.ns * 256; i += 256) {
+    const int tap = i >> 8;
+    const int r = c.r0 + 2 * (tap / c.ns), s = c.s0 + 2 * (tap % c.ns);
+    wl[i] = a.wp[(r * 7 + s) * 256 + (i & 255)];
+  }
+  for (int i = lane; i < 8 * kVsdPix; i += 64) ring[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+  __syncthreads();
+  const int m0 = (c.blk * 4 + wave) * kVsdPix;
+  int h[kVsdPT], x[kVsdPT];
+  bool ok[kVsdPT];
+#pragma unroll
+  for (int pt = 0; pt < kVsdPT; ++pt) {
+    const int m = m0 + pt * 16 + (lane & 15);
+    ok[pt] = m < c.Mc;
+    const int hc = ok[pt] ? m / c.Wc : 0;
+    h[pt] = 2 * hc + c.ph;
+    x[pt] = ok[pt] ? 2 * (m - hc * c.Wc) + c.pw : 0;
+  }
+  for (int t = 0; t < a.T + 3; ++t) {
+    if (t < a.T) {
+      f32x4 acc[kVsdPT][2];
+#pragma unroll
+      for (int pt = 0; pt < kVsdPT; ++pt)
+#pragma unroll
+        for (int jt = 0; jt < 2; ++jt) acc[pt][jt] = f32x4{0.f, 0.f, 0.f, 0.f};
+      const bf16_t* fr = a.gy + ((size_t)n * a.T + t) * a.P * a.Q * 64 + g * 8;
+      for (int ia = 0; ia < c.nr; ++ia)
+        for (int ib = 0; ib < c.ns; ++ib) {
+          const u32x4* src[kVsdPT];
+#pragma unroll
+          for (int pt = 0; pt < kVsdPT; ++pt) {
+            const int p = (h[pt] + 3 - (c.r0 + 2 * ia)) >> 1, q = (x[pt] + 3 - (c.s0 + 2 * ib)) >> 1;
+            const bool in = ok[pt] && p >= 0 && p < a.P && q >= 0 && q < a.Q;
+            src[pt] = in ? reinterpret_cast<const u32x4*>(fr + ((size_t)p * a.Q + q) * 64) : nullptr;
+          }
+          const u32x4* wt = wl + (ia * c.ns + ib) * 256 + lane;
+#pragma unroll
+          for (int kh = 0; kh < 2; ++kh) {
+            const bf16x8 a0 = __builtin_bit_cast(bf16x8, wt[(kh * 2 + 0) * 64]);
+            const bf16x8 a1 = __builtin_bit_cast(bf16x8, wt[(kh * 2 + 1) * 64]);
+#pragma unroll
+            for (int pt = 0; pt < kVsdPT; ++pt) {
+              const u32x4 bv = src[pt] ? src[pt][kh * 4] : u32x4{0u, 0u, 0u, 0u};  // + 32 channels
+              const bf16x8 b = __builtin_bit_cast(bf16x8, bv);
+              acc[pt][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, b, acc[pt][0], 0, 0, 0);
+              acc[pt][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1, b, acc[pt][1], 0, 0, 0);
+            }
+          }
+        }
+#pragma unroll
+      for (int jt = 0; jt < 2; ++jt) {
+        const int kt = jt * 4 + g, tau = t + kt - 3;
+        if (kt < 7 && tau >= 0 && tau < a.T) {
+#pragma unroll
+          for (int pt = 0; pt < kVsdPT; ++pt) {
+            float4* d = ring + (tau & 7) * kVsdPix + pt * 16 + (lane & 15);
+            float4 v = *d;
+            v.x += acc[pt][jt][0];
+            v.y += acc[pt][jt][1];
+            v.z += acc[pt][jt][2];
+            *d = v;
+          }
+        }
+      }
+    }
+    __syncthreads();
+    const int tau = t - 3;  // complete: frames tau - 3 .. tau + 3 have been added
+    if (tau >= 0) {
+      const float* slot = reinterpret_cast<const float*>(ring + (tau & 7) * kVsdPix);
+      for (int i = lane; i < 3 * kVsdPix; i += 64) {
+        const int ch = i / kVsdPix, px = i - ch * kVsdPix, m = m0 + px;
+        if (m < c.Mc) {
+          const int hc = m / c.Wc;
+          a.gx[((((size_t)n * 3 + ch) * a.T + tau) * a.H + 2 * hc + c.ph) * a.W + 2 * (m - hc * c.Wc) + c.pw] =
+              slot[px * 4 + ch];
+        }
+      }
+    }
+    __syncthreads();
+    if (tau >= 0)
+      for (int i = lane; i < kVsdPix; i += 64) ring[(tau & 7) * kVsdPix + i] = make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+}
+
+// The A fragments of form 1: out[(r*7 + s)][k half][j tile][lane][e] = bf16(w[k][c][kt][r][s]) with
+// k = 32 * half + 8 * (lane >> 4) + e and j = 16 * tile + (lane & 15) = kt * 4 + c (zero for kt = 7 and c = 3)
+__global__ __launch_bounds__(256) void pack_video_stem_dgrad_kernel(const float* __restrict__ w,
+                                                                    bf16_t* __restrict__ out) {
+  const int total = 49 * 4 * 64 * 8;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
+    const int e = i & 7, lane = (i >> 3) & 63, jt = (i >> 9) & 1, kh = (i >> 10) & 1, rs = i >> 11;
+    const int k = 32 * kh + 8 * (lane >> 4) + e, j = 16 * jt + (lane & 15), kt = j >> 2, ch = j & 3;
+    out[i] = f2bf(kt < 7 && ch < 3 ? w[(((size_t)k * 3 + ch) * 7 + kt) * 49 + rs] : 0.f);
+  }
+}
+
+static int g_video_stem_dgrad = -1;  // -1 = env AVT_VIDEO_STEM_DGRAD (default 1, the MFMA form)
+static int video_stem_dgrad_form() {
+  if (g_video_stem_dgrad < 0) {
+    const char* e = getenv("AVT_VIDEO_STEM_DGRAD");
+    g_video_stem_dgrad = e ? (atoi(e) ? 1 : 0) : 1;
+  }
+  return g_video_stem_dgrad;
+}
+
 static int grid_for(long long n) {
   long long g = (n + 255) / 256;
   if (g > 8192) g = 8192;
@@ -445,6 +659,61 @@ extern "C" int avt_stem3d_wgrad_unfold(const float* dwf, float* dw, int K, int C
   hipLaunchKernelGGL(stem3d_wgrad_unfold_kernel, dim3(grid_for((long long)K * C * KT * R * S)), dim3(256), 0,
                      (hipStream_t)stream, dwf, dw, K, C, KT, R, S);
   return check_launch("stem3d_wgrad_unfold");
+}
+
+extern "C" int avt_set_video_stem_dgrad(int form) {
+  AVT_REQUIRE(form >= -1 && form <= 1, "set_video_stem_dgrad: form=%d (-1, 0 or 1)", form);
+  avt::g_video_stem_dgrad = form;
+  return AVT_OK;
+}
+
+extern "C" size_t avt_video_stem_dgrad_pack_bytes(void) { return (size_t)49 * 4096; }
+
+extern "C" int avt_pack_video_stem_dgrad(const float* w, void* out, void* stream) {
+  AVT_REQUIRE(w && out, "pack_video_stem_dgrad: null pointer");
+  AVT_REQUIRE(((uintptr_t)out & 15) == 0, "pack_video_stem_dgrad: out must be 16-byte aligned");
+  hipLaunchKernelGGL(pack_video_stem_dgrad_kernel, dim3(49 * 8), dim3(256), 0, (hipStream_t)stream, w, (bf16_t*)out);
+  return check_launch("pack_video_stem_dgrad");
+}
+
+extern "C" int avt_video_stem_dgrad(const void* gy, const float* w, const void* wpack, float* gx, int N, int T, int H,
+                                    int W, void* stream) {
+  const int form = video_stem_dgrad_form();
+  AVT_REQUIRE(gy && gx, "video_stem_dgrad: null pointer");
+  AVT_REQUIRE(form ? wpack != nullptr : w != nullptr, "video_stem_dgrad: form %d needs %s", form,
+              form ? "wpack (avt_pack_video_stem_dgrad)" : "the fp32 weight");
+  AVT_REQUIRE(N >= 0 && N <= 65535 && T >= 1 && H >= 1 && W >= 1, "video_stem_dgrad: N=%d T=%d H=%d W=%d", N, T, H, W);
+  AVT_REQUIRE((((uintptr_t)gy | (uintptr_t)wpack) & 15) == 0, "video_stem_dgrad: gy and wpack must be 16-byte aligned");
+  const int P = (H - 1) / 2 + 1, Q = (W - 1) / 2 + 1;
+  AVT_REQUIRE((long long)N * T * P * Q * 64 * 2 < (1ll << 31) && (long long)N * 3 * T * H * W * 4 < (1ll << 31),
+              "video_stem_dgrad: activation tensors must stay below 2 GiB (32-bit buffer offsets)");
+  if (N == 0) return AVT_OK;
+  VsdArgs a{};
+  a.gy = (const bf16_t*)gy;
+  a.w = w;
+  a.wp = (const u32x4*)wpack;
+  a.gx = gx;
+  a.T = T;
+  a.H = H;
+  a.W = W;
+  a.P = P;
+  a.Q = Q;
+  const int order[4] = {3, 2, 1, 0};  // (odd, odd): 16 taps, then 12, 12, 9
+  int nb = 0;
+  for (int i = 0; i < 4; ++i) {
+    const int ph = order[i] >> 1, pw = order[i] & 1;
+    const long long Mc = (long long)((H - ph + 1) / 2) * ((W - pw + 1) / 2);  // 0: an empty class (H or W of 1)
+    const long long blocks = form ? (Mc + 4 * kVsdPix - 1) / (4 * kVsdPix) : (Mc * T + 255) / 256;
+    a.cls[i] = order[i];
+    a.first[i] = nb;
+    nb += (int)blocks;
+  }
+  a.first[4] = nb;
+  if (form)
+    hipLaunchKernelGGL(video_stem_dgrad_mfma_kernel, dim3(nb, N), dim3(256), kVsdLds, (hipStream_t)stream, a);
+  else
+    hipLaunchKernelGGL(video_stem_dgrad_direct_kernel, dim3(nb, N), dim3(256), 0, (hipStream_t)stream, a);
+  return check_launch("video_stem_dgrad");
 }
 
 extern "C" size_t avt_pack3d_desc_bytes(void) { return sizeof(Pack3dDesc); }

@@ -12,8 +12,12 @@ Forward only by default: FullModel detaches the video trunk, so a call that woul
 standalone module becomes trainable with ``net.enable_backward()`` (fine-tuning or pre-training the trunk the
 reference loads Kinetics weights into, train_3D.py:89): every parameter then receives its gradient from libavt's
 Conv3d dgrad / wgrad, BatchNorm and max-pool backward kernels (tube.R3DTrunk.backward) through one
-``autograd.Function``, and ``torch.optim`` optimizers work on ``net.parameters()`` (views of the flat store).  No
-gradient is computed for the video itself.
+``autograd.Function``, and ``torch.optim`` optimizers work on ``net.parameters()`` (views of the flat store).
+Two further opt-ins, both off by default: ``net.enable_backward(input_grad=True)`` also returns the gradient of a video
+that requires grad (``video.grad``, fp32 [b,3,t,H,W], through libavt's ``avt_video_stem_dgrad``: saliency /
+attribution over a clip, adversarial or consistency training, a learnable module in front of the trunk -- it works
+with every parameter frozen); ``net.enable_backward(eval_grad=True)`` differentiates an eval-mode trunk (BatchNorm
+frozen on its running statistics, which are read and never updated: ``avt_bn_eval_bwd``).
 """
 from __future__ import annotations
 
@@ -82,6 +86,8 @@ class ResNet(nn.Module):
         self._avt_engine = None
         self._own_flat = None  # a standalone module's flat storage, created at its first .to() / forward
         self._avt_backward = False  # enable_backward(): every parameter trainable (standalone modules only)
+        self._avt_input_grad = False  # enable_backward(input_grad=True): a video that requires grad gets its gradient
+        self._avt_eval_grad = False  # enable_backward(eval_grad=True): eval-mode (running-statistics BN) backward
 
     def _make_layer(self, block, planes, blocks, stride=1):
         downsample = None  # built before the block, as resnet3D.py:169-184 (RNG order)
@@ -112,10 +118,14 @@ class ResNet(nn.Module):
             self._own_flat = FlatStore(self, (lambda n: True) if self._avt_backward else (lambda n: False))
         return self._own_flat
 
-    def enable_backward(self):
+    def enable_backward(self, input_grad: bool = False, eval_grad: bool = False):
         """Make this standalone trunk trainable: its flat store is rebuilt with every parameter in the trainable
-        segment, and grad-mode calls in train mode go through the backward kernels.  Raises on a trunk adopted by a
-        FullModel (the reference detaches that trunk, model.py:14; the tube step computes no video gradients)."""
+        segment, and grad-mode calls in train mode go through the backward kernels.  input_grad=True: a video that
+        requires grad also receives its gradient (fp32, the video's layout; one that does not costs nothing more).
+        eval_grad=True: grad-mode calls of an eval-mode trunk are differentiated too, BatchNorm by its
+        running-statistics rule (no running statistic or num_batches_tracked changes).  A later call can only widen
+        the opt-in, and rebuilds nothing once the trunk is trainable.  Raises on a trunk adopted by a FullModel (the
+        reference detaches that trunk, model.py:14; the tube step computes no video gradients)."""
         if self._avt_parent is not None:
             raise RuntimeError("avt: enable_backward() is for a standalone R3D trunk; FullModel.vidnet is detached "
                                "(model.py:14) and stays forward-only")
@@ -126,6 +136,8 @@ class ResNet(nn.Module):
 
                 self._own_flat = FlatStore(self, lambda n: True)
             self._avt_engine = None
+        self._avt_input_grad = self._avt_input_grad or bool(input_grad)
+        self._avt_eval_grad = self._avt_eval_grad or bool(eval_grad)
         return self
 
     def _apply(self, fn, recurse=True):
@@ -141,23 +153,25 @@ class ResNet(nn.Module):
         from .tube import R3DEngine
 
         need_grad = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters()))
-        if need_grad and x.requires_grad:
+        if need_grad and x.requires_grad and not self._avt_input_grad:
             raise NotImplementedError("avt: no input gradient is computed for the video of the R3D trunk; pass a video "
-                                      "tensor that does not require grad")
+                                      "tensor that does not require grad (a standalone trunk computes it after "
+                                      "net.enable_backward(input_grad=True))")
         if need_grad and not (self._avt_backward and self._avt_parent is None):
             raise NotImplementedError("avt: the R3D trunk is forward-only in this build (FullModel detaches it); "
                                       "call it under torch.no_grad() or with requires_grad_(False) parameters.  A "
                                       "standalone trunk becomes trainable after net.enable_backward().")
-        if need_grad and not self.training:
+        if need_grad and not self.training and not self._avt_eval_grad:
             raise NotImplementedError("avt: gradients through an eval-mode trunk are not computed (train-mode "
-                                      "BatchNorm only)")
+                                      "BatchNorm only; a standalone trunk computes them after "
+                                      "net.enable_backward(eval_grad=True))")
         if need_grad:
             flat = self._flat_store()
             if self._avt_engine is None or self._avt_engine.flat is not flat or not self._avt_engine.with_backward:
                 self._avt_engine = R3DEngine(flat, "", max_pool=not self.no_max_pool, with_backward=True)
             named = dict(self.named_parameters())
             names = [n for n in flat.pnames if named[n].requires_grad]
-            return _R3DFunction.apply(self._avt_engine, names, x, *[named[n] for n in names])
+            return _R3DFunction.apply(self._avt_engine, names, self.training, x, *[named[n] for n in names])
         if self._avt_parent is not None:
             parent, prefix = self._avt_parent[0](), self._avt_parent[1]
             if parent is None or getattr(parent, prefix.rstrip("."), None) is not self:
@@ -172,27 +186,31 @@ class ResNet(nn.Module):
 
 class _R3DFunction(torch.autograd.Function):
     """Bridge of a trainable standalone trunk into autograd (as model._TrunkFunction): forward keeps the engine's
-    tape, backward returns the per-parameter views of one flat gradient buffer."""
+    tape, backward returns the per-parameter views of one flat gradient buffer (None for a parameter that is not an
+    input: one with requires_grad False) and, for a video that requires grad, its gradient."""
 
     @staticmethod
-    def forward(ctx, engine, names, x, *params):
-        out, tape = engine.forward(x, True, tape=True)
-        ctx.engine, ctx.tape, ctx.names = engine, tape, names
+    def forward(ctx, engine, names, training, x, *params):
+        want_gx = ctx.needs_input_grad[3]
+        out, tape = engine.forward(x.detach(), training, tape=True, input_grad=want_gx)
+        ctx.engine, ctx.tape, ctx.names, ctx.want_gx, ctx.x_dtype = engine, tape, names, want_gx, x.dtype
         ctx.set_materialize_grads(False)
         return out
 
     @staticmethod
     def backward(ctx, g):
         if g is None:
-            return (None, None, None) + (None,) * len(ctx.names)
+            return (None, None, None, None) + (None,) * len(ctx.names)
         if ctx.tape is None:
             raise RuntimeError("avt: second backward through a trunk forward")
         flat = ctx.engine.flat
         gflat = torch.zeros(flat.n_train, device=g.device, dtype=torch.float32)
-        ctx.engine.backward(ctx.tape, g, gflat)
+        gx = ctx.engine.backward(ctx.tape, g, gflat, want_gvideo=ctx.want_gx)
         ctx.tape = None
         views = flat.param_grad_views(gflat)
-        return (None, None, None) + tuple(views[n] for n in ctx.names)
+        if gx is not None and gx.dtype != ctx.x_dtype:
+            gx = gx.to(ctx.x_dtype)
+        return (None, None, None, gx) + tuple(views[n] for n in ctx.names)
 
 
 def generate_model(model_depth, **kwargs):

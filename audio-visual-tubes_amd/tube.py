@@ -31,7 +31,9 @@ from typing import Dict, List, Optional
 
 import torch
 
-from ._lib import call, query
+import ctypes
+
+from ._lib import BnBwdTarget, call, query
 from .engine import AVEngine, FlatStore, _EngineStore
 from .trunk import BNSpec, ConvProfiler, P, Trunk, _bn_finalize, conv_out, stream_ptr
 
@@ -184,8 +186,34 @@ class R3DTrunk:
 
     # ------------------------------------------------------------------ backward
     @staticmethod
-    def _bn_bwd(g, y, xc, stats, bn: BNSpec, store, gmask_out=None):
-        """avt_bn_bwd: g' = g * [y > 0] (y None: no mask) -> the gradient of the pre-BN activation xc; d(gamma, beta)."""
+    def _eval_target(xc, stats, bn: BNSpec, store):
+        """(avt_bn_bwd_target of one eval-mode BN, its gc): stats = the running-statistics (scale, shift, mean, invstd)."""
+        t, gc = BnBwdTarget(), torch.empty_like(xc)
+        t.xc, t.mean, t.invstd, t.gc = xc.data_ptr(), stats[2].data_ptr(), stats[3].data_ptr(), gc.data_ptr()
+        t.gamma = store.param(bn.prefix + ".weight").data_ptr()
+        t.dgamma, t.dbeta = store.grad(bn.prefix + ".weight").data_ptr(), store.grad(bn.prefix + ".bias").data_ptr()
+        t.workspace = store.stat_acc(bn, "bwd", xc.numel() // bn.c).data_ptr()
+        return t, gc
+
+    @classmethod
+    def _bn_eval_bwd(cls, g, y, mask_stats, xc, stats, bn: BNSpec, store, gmask_out=None, second=None):
+        """avt_bn_eval_bwd: the running-statistics rule gc = gamma * invstd * g' (one pass).  Mask from y, from
+        mask_stats = (scale, shift) on xc, or none; second = (xc2, stats2, bn2): a BN sharing g' -> (gc, gc2)."""
+        t1, gc = cls._eval_target(xc, stats, bn, store)
+        t2 = gc2 = None
+        if second is not None:
+            t2, gc2 = cls._eval_target(second[0], second[1], second[2], store)
+        ms = (None, None) if mask_stats is None else (mask_stats[0], mask_stats[1])
+        call("avt_bn_eval_bwd", P(g), P(y), P(ms[0]), P(ms[1]), ctypes.byref(t1),
+             ctypes.byref(t2) if t2 is not None else None, P(gmask_out), xc.numel() // bn.c, bn.c, stream_ptr())
+        return gc if second is None else (gc, gc2)
+
+    @classmethod
+    def _bn_bwd(cls, g, y, xc, stats, bn: BNSpec, store, gmask_out=None, training=True):
+        """avt_bn_bwd: g' = g * [y > 0] (y None: no mask) -> the gradient of the pre-BN activation xc; d(gamma, beta).
+        training=False: the eval-mode rule (avt_bn_eval_bwd)."""
+        if not training:
+            return cls._bn_eval_bwd(g, y, None, xc, stats, bn, store, gmask_out=gmask_out)
         rows = xc.numel() // bn.c
         gc = torch.empty_like(xc)
         call("avt_bn_bwd", P(g), P(y), P(xc), P(stats[2]), P(stats[3]), P(store.param(bn.prefix + ".weight")),
@@ -193,9 +221,11 @@ class R3DTrunk:
              P(store.stat_acc(bn, "bwd", rows)), rows, bn.c, stream_ptr())
         return gc
 
-    @staticmethod
-    def _bn_relu_bwd(g, xc, stats, bn: BNSpec, store):
+    @classmethod
+    def _bn_relu_bwd(cls, g, xc, stats, bn: BNSpec, store, training=True):
         """bn -> relu backward, the mask recomputed from (xc, scale, shift) as the forward's avt_bn_apply made it."""
+        if not training:
+            return cls._bn_eval_bwd(g, None, stats, xc, stats, bn, store)
         rows = xc.numel() // bn.c
         gc = torch.empty_like(xc)
         call("avt_bn_relu_bwd", P(g), P(xc), P(stats[0]), P(stats[1]), P(stats[2]), P(stats[3]),
@@ -235,26 +265,35 @@ class R3DTrunk:
                          2.0 * (gy.numel() + wt.numel() + gx.numel()))
         return gx
 
-    def backward(self, tape, g: torch.Tensor, store) -> None:
+    def backward(self, tape, g: torch.Tensor, store, training: bool = True, gvideo=None) -> None:
         """g bf16 [b*T, h, w, 512] = d(loss)/d(layer4 map) -> the trunk's parameter gradients, accumulated into
         store.grad(name) (zeroed by the caller).  Blocks in reverse, unfused (autograd through BasicBlock.forward,
         resnet3D.py:45-61): bn2 (+ downsample.1) backward, conv2 wgrad + dgrad, bn1+relu backward, conv1 wgrad + dgrad
         with the residual gradient (identity: added in the dgrad's store; strided block: the in-place 2-D dgrad of
-        the 1x1x1 downsample), then the stem's max-pool / BN+ReLU backward and its folded weight gradient.  No
-        input gradient is computed for the video."""
+        the 1x1x1 downsample), then the stem's max-pool / BN+ReLU backward and its folded weight gradient.
+        training=False: the tape of an eval-mode forward, every BatchNorm backward by the running-statistics rule
+        (avt_bn_eval_bwd; a first block's bn2 + downsample.1 in one pass).  gvideo (fp32 [b,3,t,H,W], optional)
+        receives the video's gradient (avt_video_stem_dgrad on the stem's gc0)."""
         b = tape["b"]
         for blk, tb in zip(reversed(self.blocks), reversed(tape["blocks"])):
             T, H, W, Ho, Wo = tb["dims"]
-            gm = torch.empty_like(g)  # g * [out > 0]: shared by bn2, downsample.1 and the identity residual
-            gc2 = self._bn_bwd(g, tb["out"], tb["c2"], tb["s2"], blk["bn2"], store, gmask_out=gm)
+            gm = gcd = None
+            if training or blk["down"] is None:
+                gm = torch.empty_like(g)  # g * [out > 0]: shared by bn2, downsample.1 and the identity residual
+                gc2 = self._bn_bwd(g, tb["out"], tb["c2"], tb["s2"], blk["bn2"], store, gmask_out=gm,
+                                   training=training)
+            else:
+                gc2, gcd = self._bn_eval_bwd(g, tb["out"], None, tb["c2"], tb["s2"], blk["bn2"], store,
+                                             second=(tb["cd"], tb["sd"], blk["bnd"]))
             self._wgrad(tb["h1"], gc2, b, T, Ho, Wo, blk["conv2"], store)
             gh1 = self._dgrad(gc2, b, T, Ho, Wo, blk["conv2"], store)
             del gc2
-            gc1 = self._bn_relu_bwd(gh1, tb["c1"], tb["s1"], blk["bn1"], store)
+            gc1 = self._bn_relu_bwd(gh1, tb["c1"], tb["s1"], blk["bn1"], store, training=training)
             del gh1
             self._wgrad(tb["x"], gc1, b, T, H, W, blk["conv1"], store)
             if blk["down"] is not None:
-                gcd = self._bn_bwd(gm, None, tb["cd"], tb["sd"], blk["bnd"], store)
+                if gcd is None:
+                    gcd = self._bn_bwd(gm, None, tb["cd"], tb["sd"], blk["bnd"], store)
                 self._wgrad(tb["x"], gcd, b, T, H, W, blk["down"], store)
                 g = self._dgrad(gc1, b, T, H, W, blk["conv1"], store)
                 dn = blk["down"]
@@ -267,7 +306,7 @@ class R3DTrunk:
             gp = torch.empty_like(tape["h0"])
             call("avt_maxpool3d_bwd", P(g), P(tape["h0"]), None, P(gp), b, T, H, W, 64, stream_ptr())
             g = gp
-        gc0 = self._bn_relu_bwd(g, tape["c0"], tape["s0"], self.bn1, store)
+        gc0 = self._bn_relu_bwd(g, tape["c0"], tape["s0"], self.bn1, store, training=training)
         # the stem's weight gradient in its folded layout: a 2-D wgrad over the 32-channel im2col input, unfolded
         st, x = self.stem, tape["x"]
         Ti, Hi, Wi = tape["dims"]
@@ -278,6 +317,12 @@ class R3DTrunk:
              P(ws), wsb, stream_ptr())
         call("avt_stem3d_wgrad_unfold", P(dwf), P(store.grad(st.name)), st.cout, st.cin, st.kt, st.k, st.k,
              stream_ptr())
+        if gvideo is not None:  # d(loss)/d(video), fp32 NCDHW
+            ev = ConvProfiler.begin()
+            call("avt_video_stem_dgrad", P(gc0), P(store.param(st.name)), P(store.packed3d_t(st)), P(gvideo), b, Ti, Hi,
+                 Wi, stream_ptr())
+            ConvProfiler.end(ev, "dgrad3d", 2.0 * gvideo.numel() * (st.kt * st.k * st.k / 4.0) * st.cout,
+                             2.0 * gc0.numel() + 4.0 * gvideo.numel())
 
 
 def _alloc_packs3d(engine, dev):
@@ -312,9 +357,10 @@ def _alloc_packs3d(engine, dev):
         engine._pack3d_t_n, engine._pack3d_t_blocks = len(descs), max_blocks
 
 
-def _pack3d(engine):
+def _pack3d(engine, stem_dgrad: bool = False):
     """vidnet weights (fp32 OIDHW, never updated by the optimizer) -> bf16 fwd operands, repacked every step so a
-    load_state_dict is always picked up: the folded stem (its own layout) and one launch for the other 19 convs."""
+    load_state_dict is always picked up: the folded stem (its own layout) and one launch for the other 19 convs.
+    stem_dgrad (a step whose video requires grad): the stem's dgrad operand too (avt_video_stem_dgrad's MFMA form)."""
     stem = engine.vid.stem
     call("avt_pack_conv3d_weight", P(engine.flat.raw(stem.name)), P(engine.packs3d[stem.name]), stem.cout, stem.cin,
          stem.kt, stem.k, stem.k, 1, stream_ptr())
@@ -323,6 +369,12 @@ def _pack3d(engine):
     if engine._pack3d_t_table is not None:  # a trainable trunk: the dgrad operands too (one more launch)
         call("avt_pack_conv3d_weights_dgrad_batched", P(engine._pack3d_t_table), engine._pack3d_t_n,
              engine._pack3d_t_blocks, stream_ptr())
+        if stem_dgrad:
+            if stem.name not in engine.packs3d_t:
+                engine.packs3d_t[stem.name] = torch.empty(int(query("avt_video_stem_dgrad_pack_bytes")),
+                                                          device=engine.flat.flat.device, dtype=torch.uint8)
+            call("avt_pack_video_stem_dgrad", P(engine.flat.raw(stem.name)), P(engine.packs3d_t[stem.name]),
+                 stream_ptr())
 
 
 class _TubeStore(_EngineStore):
@@ -486,16 +538,19 @@ class R3DEngine(AVEngine):
         super()._alloc(dev)
         _alloc_packs3d(self, dev)
 
-    def pack_weights(self):
-        _pack3d(self)
+    def pack_weights(self, stem_dgrad: bool = False):
+        _pack3d(self, stem_dgrad)
 
-    def forward(self, video: torch.Tensor, training: bool, tape: bool = False):
-        """video fp32 [b,3,t,H,W] -> fc logits [b, n_classes] fp32 (tape=True: (logits, tape) for ``backward``)."""
+    def forward(self, video: torch.Tensor, training: bool, tape: bool = False, input_grad: bool = False):
+        """video fp32 [b,3,t,H,W] -> fc logits [b, n_classes] fp32 (tape=True: (logits, tape) for ``backward``; the
+        tape of a training=False forward holds the running-statistics (scale, shift, mean, invstd) and no running
+        statistic is touched).  input_grad: ``backward`` will be asked for the video's gradient (the stem's dgrad
+        operand is packed with the others)."""
         if not video.is_cuda:
             raise RuntimeError("avt: inputs must be on the GPU (no CPU path)")
         if video.dim() != 5:
             raise ValueError(f"avt: expected video [b,3,t,H,W], got {tuple(video.shape)}")
-        self.pack_weights()
+        self.pack_weights(stem_dgrad=tape and input_grad)
         if training and self._nbt_idx.numel():
             self.flat.nbt.index_add_(0, self._nbt_idx, torch.ones_like(self._nbt_idx))
         b = video.shape[0]
@@ -505,16 +560,24 @@ class R3DEngine(AVEngine):
                 raise RuntimeError("avt: this R3D engine was built forward-only")
             v, tp = self.vid.forward(video, self.store, training, tape=True)
             feat = v.view(b, -1, v.shape[-1]).float().mean(1)
-            tp.update(v_shape=tuple(v.shape), feat=feat)
+            tp.update(v_shape=tuple(v.shape), feat=feat, training=training, video_shape=tuple(video.shape),
+                      stem_dgrad=input_grad)
             return torch.addmm(bias, feat, w.t()), tp
         v = self.vid.forward(video, self.store, training)  # [(b t), h, w, 512] bf16
         feat = v.view(b, -1, v.shape[-1]).float().mean(1)  # AdaptiveAvgPool3d((1,1,1)) + flatten
         return torch.addmm(bias, feat, w.t())  # nn.Linear (resnet3D.py:212)
 
-    def backward(self, tape, glogits: torch.Tensor, gflat: torch.Tensor) -> None:
+    def backward(self, tape, glogits: torch.Tensor, gflat: torch.Tensor, want_gvideo: bool = False):
         """d(loss)/d(logits) [b, n_classes] -> the gradient of every vidnet parameter, accumulated into the flat
         buffer gflat[:n_train] (zeroed by the caller).  The fc and AdaptiveAvgPool3d backward run in torch on the
-        [b, 512] features (a few kilobytes); the rest is R3DTrunk.backward."""
+        [b, 512] features (a few kilobytes); the rest is R3DTrunk.backward, in the mode (train / eval BatchNorm) of
+        the forward that made the tape.  want_gvideo (a forward with input_grad=True): returns d(loss)/d(video),
+        fp32 [b,3,t,H,W]; otherwise None."""
+        gvideo = None
+        if want_gvideo:
+            if not tape.get("stem_dgrad"):
+                raise RuntimeError("avt: the video's gradient needs a forward(..., tape=True, input_grad=True)")
+            gvideo = torch.empty(tape["video_shape"], device=glogits.device, dtype=torch.float32)
         grads = self.flat.grad_views(gflat)
         glogits = glogits.contiguous().float()
         w = self.flat.raw(self._prefix + "fc.weight")
@@ -527,6 +590,7 @@ class R3DEngine(AVEngine):
         g = gfeat.to(torch.bfloat16).view(b, 1, C).expand(b, per, C).contiguous().view(n, h, wd, C)
         self.store.grads = grads
         try:
-            self.vid.backward(tape, g, self.store)
+            self.vid.backward(tape, g, self.store, training=tape.get("training", True), gvideo=gvideo)
         finally:
             self.store.grads = None
+        return gvideo

@@ -228,6 +228,18 @@ int avt_maxpool3d_bwd(const void* gy, const void* x, const void* y, void* gx, in
  * avt_conv2d_wgrad's result over the folded input of avt_video_stem_im2col (Cp = Creal = 32, with its workspace:
  * deterministic); dw[k][c][kt][r][s] (fp32 OIDHW [K][C][KT][R][S]) += dwf[k][r][s][kt*4 + c] */
 int avt_stem3d_wgrad_unfold(const float* dwf, float* dw, int K, int C, int KT, int R, int S, void* stream);
+/* R3D stem Conv3d(3,64,(7,7,7),s(1,2,2),p3) input gradient (resnet3D.py:122-127 under autograd, when the video requires
+ * grad): gx[N][3][T][H][W] fp32 (NCDHW, the video's layout) = conv3d_input(gy[N,T,P,Q,64] bf16, w), P = (H-1)/2+1,
+ * Q = (W-1)/2+1; frames outside the clip and rows/columns outside the frame contribute zero.  Two forms behind
+ * avt_set_video_stem_dgrad (avt_tuning.h): 0 = direct, fp32 weights w (OIDHW [64][3][7][7][7]), fp32 sums over
+ * (kt, r, s, k) in a fixed order; 1 = MFMA, the transpose of the forward's folded 2-D conv per (h%2, w%2) parity class
+ * with the temporal fold-back fused (no intermediate), weights rounded to bf16 in the operand `wpack`
+ * (avt_video_stem_dgrad_pack_bytes() bytes, 16-byte aligned, written by avt_pack_video_stem_dgrad -- once per step),
+ * fp32 accumulation.  Only the selected form's weight argument is read; no atomics, bitwise reproducible. */
+size_t avt_video_stem_dgrad_pack_bytes(void);
+int avt_pack_video_stem_dgrad(const float* w, void* out, void* stream);
+int avt_video_stem_dgrad(const void* gy, const float* w, const void* wpack, float* gx, int N, int T, int H, int W,
+                         void* stream);
 
 /* tube-step audio de-duplication: out[b*rep+k][:] = in[b][:]  /  out[b][:] = sum_k in[b*rep+k][:] */
 int avt_repeat_rows_f32(const float* in, float* out, int B, int rep, int C, void* stream);
@@ -274,6 +286,14 @@ typedef struct {
  * reading g and the mask once for both */
 int avt_bn_bwd_mask(const void* g, const void* mask, const avt_bn_bwd_target* t1, const avt_bn_bwd_target* t2,
                     long long rows, int C, void* stream);
+/* Eval-mode (running-statistics) BatchNorm backward, one pass: g' = g * mask; per target (t2 optional, sharing g': a
+ * first block's bn2 + downsample.1) gc = gamma*invstd*g', dbeta += sum g', dgamma += sum g'*(xc - mean)*invstd with
+ * mean = running_mean, invstd = rsqrt(running_var + eps) -- no mean-subtraction terms.  Mask: y > 0 if y != NULL, else
+ * fma(t1->xc, mscale, mshift) > 0 if mscale != NULL (as avt_bn_relu_bwd), else none; gmask_out (optional) = g'.  The
+ * sums go through the target's fixed-order slot workspace (avt_bn_bwd_workspace; bitwise reproducible); a target with
+ * dgamma == dbeta == NULL needs no workspace and is purely elementwise. */
+int avt_bn_eval_bwd(const void* g, const void* y, const float* mscale, const float* mshift, const avt_bn_bwd_target* t1,
+                    const avt_bn_bwd_target* t2, void* gmask_out, long long rows, int C, void* stream);
 /* avt_bn_bwd for a g' that is already masked and whose reductions a dgrad epilogue already added
  * into the workspace (avt_conv2d_dgrad_bn): finalize + apply only */
 int avt_bn_bwd_premasked(const void* gm, const void* xc, const float* mean, const float* invstd, const float* gamma,

@@ -94,6 +94,10 @@ int avt_set_stem_kernel(int on);
 /* 1 (default, env AVT_STEM_WGRAD): the 7x7/s2 stem wgrads (C 4 or 1, K 64) run on the per-wave
  * LDS-patch kernel (needs the avt_conv2d_wgrad_workspace() slab; deterministic); 0: the generic one */
 int avt_set_stem_wgrad(int on);
+/* avt_video_stem_dgrad's form: 1 (default, env AVT_VIDEO_STEM_DGRAD) = the per-parity-class MFMA kernel with the fused
+ * temporal fold-back (bf16 weights), 0 = the direct fp32-weight kernel (one thread per voxel; the A/B partner and
+ * reference form); -1: back to the environment default.  Returns AVT_EINVAL outside -1..1 */
+int avt_set_video_stem_dgrad(int form);
 int avt_set_halo_splitk(int ksplit, int target_blocks);
 /* TN wgrad LDS ring depth: nst for the 4-wave tiles (4 default, 6, 8), nst_big for the 8-wave 256 x 256
  * tile (3 default, 4, 5) -- deeper rings keep more k-tiles in flight for a block alone on its CU */

@@ -54,11 +54,39 @@ def bench_bwd(b, T, dev):
               f"{flops / g / 1e9:5.0f} TF/s ({g * 1e3:7.1f} us, slab {wsb / 2 ** 20:.1f} MiB)", flush=True)
 
 
+def bench_stem_dgrad(b, T, size, dev):
+    """The stem's input gradient avt_video_stem_dgrad in both forms (0 direct, 1 MFMA) next to the stem's weight
+    gradient launch over the same gy (avt_conv2d_wgrad over the folded 32-channel input: the same-volume yardstick).
+    TFLOP/s counts the folded GEMM's useful flops, 2 N T H W (343 / 4) 64 3."""
+    H = W = size
+    Ho = (H - 1) // 2 + 1
+    gy = torch.randn(b, T, Ho, Ho, 64, device=dev).to(torch.bfloat16)
+    w = torch.randn(64, 3, 7, 7, 7, device=dev) * 0.01
+    wp = torch.empty(int(query("avt_video_stem_dgrad_pack_bytes")), device=dev, dtype=torch.uint8)
+    call("avt_pack_video_stem_dgrad", P(w), P(wp), S())
+    gx = torch.empty(b, 3, T, H, W, device=dev)
+    x = torch.randn(b, T, H, W, 32, device=dev).to(torch.bfloat16)
+    dwf = torch.zeros(64, 7, 7, 32, device=dev)
+    wsb = int(query("avt_conv2d_wgrad_workspace", b * T, H, W, 32, 32, 64, 7, 7, 2, 3))
+    ws = torch.empty(max(wsb, 16), device=dev, dtype=torch.uint8)
+    flops = 2.0 * b * T * H * W * (343 / 4.0) * 64 * 3
+    line = f"stem 7x7x7 {size:3d}^2 b={b} t={T} |"
+    for form in (0, 1):
+        call("avt_set_video_stem_dgrad", form)
+        ms = timeit(lambda: call("avt_video_stem_dgrad", P(gy), P(w), P(wp), P(gx), b, T, H, W, S()))
+        line += f" input grad form {form} {flops / ms / 1e9:6.1f} TF/s ({ms * 1e3:8.1f} us) |"
+    call("avt_set_video_stem_dgrad", -1)
+    ms = timeit(lambda: call("avt_conv2d_wgrad", P(x), P(gy), P(dwf), b * T, H, W, 32, 32, 64, 7, 7, 2, 3, P(ws), wsb,
+                             S()))
+    print(line + f" folded wgrad ({ms * 1e3:8.1f} us)", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--mode", default="fwd", choices=["fwd", "bwd"])
     ap.add_argument("--clips", type=int, default=8)
     ap.add_argument("--frames", type=int, default=16)
+    ap.add_argument("--stem-sizes", default="224,112", help="--mode bwd: frame sizes of the stem input-gradient row")
     ap.add_argument("--nt64", default="-1")
     ap.add_argument("--nt128", default="-1")
     ap.add_argument("--halo3d", default="1,0", help="avt_set_halo3d values to sweep (1: the halo Conv3d form where it "
@@ -73,6 +101,8 @@ def main():
     torch.cuda.synchronize()
     if args.mode == "bwd":
         bench_bwd(b, T, dev)
+        for size in [int(v) for v in args.stem_sizes.split(",") if v]:
+            bench_stem_dgrad(b, T, size, dev)
         return
     for name, H, W, C, K, st in SHAPES:
         Ho, Wo = (H + 2 - 3) // st + 1, (W + 2 - 3) // st + 1
