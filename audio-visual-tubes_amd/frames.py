@@ -23,7 +23,11 @@ from .trunk import P, stream_ptr
 
 MEAN = (0.485, 0.456, 0.406)
 STD = (0.229, 0.224, 0.225)
-MAX_DOWNSCALE = 7.5  # <= 32 bicubic taps per output pixel (csrc/frames.hip)
+MAX_DOWNSCALE = 7.5  # supported factor of the resize (its short side)
+# One axis alone may go up to 8: a factor f needs at most ceil(4 f) bicubic taps per output pixel and
+# csrc/frames.hip holds FR_KMAX = 32.  Resize(int) truncates the long side, int(size * long / short),
+# so that axis shrinks a little more than the short one (700x240 -> 93x32: 7.53 for a 7.5 resize).
+MAX_AXIS_DOWNSCALE = 8.0
 
 
 def resized_size(w: int, h: int, size: int) -> tuple[int, int]:
@@ -85,7 +89,7 @@ class FrameTransform:
             H, W = f.shape[0], f.shape[1]
             if not (0 <= ci <= rh - s and 0 <= cj <= rw - s):
                 raise ValueError(f"avt: crop ({ci}, {cj}) of {s} outside the {rw}x{rh} resized frame")
-            if H / rh > MAX_DOWNSCALE or W / rw > MAX_DOWNSCALE:
+            if min(H / rh, W / rw) > MAX_DOWNSCALE or max(H / rh, W / rw) > MAX_AXIS_DOWNSCALE:
                 raise ValueError(f"avt: downscale {W}x{H} -> {rw}x{rh} exceeds {MAX_DOWNSCALE}x")
             desc[i] = (off, H, W, rh, rw, ci, cj, int(bool(flip)))
             off += H * W * 3

@@ -32,11 +32,12 @@ def clip_wave(samples: np.ndarray, samplerate: int) -> np.ndarray:
     return resamples
 
 
-def reference_spectrogram(resamples: np.ndarray, samplerate: float) -> np.ndarray:
-    """The reference's own calls (scipy) on an already clipped waveform -> [1, 257, nseg] float64."""
+def reference_spectrogram(resamples: np.ndarray, samplerate: float, noverlap: int = NOVERLAP) -> np.ndarray:
+    """The reference's own calls (scipy) on an already clipped waveform -> [1, 257, nseg] float64.
+    `noverlap` other than the reference's 1 checks the kernel's other hops."""
     from scipy import signal
 
-    _, _, spec = signal.spectrogram(resamples, samplerate, nperseg=NPERSEG, noverlap=NOVERLAP)
+    _, _, spec = signal.spectrogram(resamples, samplerate, nperseg=NPERSEG, noverlap=noverlap)
     return (np.log(spec + 1e-7) / 12.0)[None]
 
 

@@ -47,6 +47,30 @@ def test_error_path_reports_message():
         _lib.call("avt_conv2d_fwd", None, None, None, None, 1, 8, 8, 64, 48, 3, 3, 1, 1, 576, None)
 
 
+def test_spectrogram_segment_count_query():
+    """avt_spectrogram_segments (host only): (N - 512) // hop + 1, and 0 for what cannot be framed."""
+    if not os.path.exists(_lib.LIB_PATH):
+        _lib.build()
+    from avt_amd.audio import num_segments
+
+    q = lambda n, hop: _lib.query("avt_spectrogram_segments", n, hop)  # noqa: E731
+    assert q(153301, 511) == num_segments(153301) == 300          # the reference's 10 s clip
+    assert [q(n, 511) for n in (0, 511, 512, 1022, 1023, 512 + 511 * 8 + 510)] == [0, 0, 1, 1, 2, 9]
+    assert (q(1024, 512), q(552, 1), q(512, 0), q(4096, -1)) == (2, 41, 0, 0)
+    assert num_segments(1024, noverlap=0) == 2 and num_segments(552, noverlap=511) == 41
+    assert q(2 ** 33, 511) == (2 ** 33 - 512) // 511 + 1          # the sample count is a long long
+
+
+def test_loss_workspace_query():
+    """avt_loss_workspace_floats (host only): 1024 per-block partial sums + one float per row."""
+    if not os.path.exists(_lib.LIB_PATH):
+        _lib.build()
+    assert _lib.query("avt_loss_workspace_floats", 1, 0) == 1024
+    assert _lib.query("avt_loss_workspace_floats", 8 * 16 * 196, 8 * 16) == 1024 + 128
+    assert _lib.query("avt_loss_workspace_floats", 2 ** 33, 2 ** 32) == 1024 + 2 ** 32   # long long arguments
+    assert _lib.query("avt_loss_workspace_floats", 10, -5) == 1024
+
+
 def test_state_dict_keys_shapes_match_reference_inventory():
     m = AVENet(orc.Args(), False)
     sd = m.state_dict()
