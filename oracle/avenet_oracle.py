@@ -123,6 +123,14 @@ def make_image(batch: int, size: int = 224, seed: int = 1) -> torch.Tensor:
     return torch.from_numpy(rng.standard_normal((batch, 3, size, size), dtype=np.float32))
 
 
+def make_gout(batch: int, h: int, w: int, seed: int = 7) -> torch.Tensor:
+    """A fixed dense standard-normal upstream gradient of a trunk's layer4 map [batch,512,h,w], rounded to bf16 once
+    (the trunk's backward takes it in bf16: both sides of a comparison then see the same values)."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    g = torch.from_numpy(rng.standard_normal((batch, 512, h, w), dtype=np.float32))
+    return g.to(torch.bfloat16).float()
+
+
 def make_spectrogram(batch: int, freq: int = 257, frames: int = 300, seed: int = 2) -> torch.Tensor:
     """log-spectrogram recipe of datasets/dataloader.py:86-96 on clipped Gaussian noise.
 
@@ -193,6 +201,117 @@ def resnet18_forward(sd, prefix: str, x: torch.Tensor, modal: str, training: boo
             x = F.relu(out + idt)
         inplanes = planes
     return x
+
+
+def _max_pool2d_last(x: torch.Tensor) -> torch.Tensor:
+    """MaxPool2d(3, 2, 1) whose gradient goes to the LAST maximum of a window in scan order (torch's own, and the
+    trunk's, go to the first): resnet18_forward_forced's "pool_last" fault."""
+    xp = F.pad(x, (1, 1, 1, 1), value=float("-inf"))
+    Ho, Wo = [(n - 1) // 2 + 1 for n in x.shape[2:]]
+    taps = torch.stack([xp[:, :, dh:dh + 2 * Ho:2, dw:dw + 2 * Wo:2] for dh in range(3) for dw in range(3)])
+    idx = 8 - taps.detach().flip(0).argmax(0, keepdim=True)  # argmax returns the first of equal maxima
+    return taps.gather(0, idx)[0]
+
+
+FORCED_FAULTS_2D = ("drop_identity", "drop_downsample", "mask_c2", "pool_last", "unmasked_class00")
+
+
+def resnet18_forward_forced(sd, prefix: str, x: torch.Tensor, modal: str, tape: dict, grad_round=None,
+                            fault: str = None) -> torch.Tensor:
+    """resnet18_forward's graph in train mode, "teacher-forced" onto a recorded forward state: for a fixed forward
+    state the backward is a linear map of the upstream gradient, so autograd through this function is the reference of
+    a trunk's backward on that trunk's OWN forward, with the forward's rounding noise (flipped ReLU masks, shifted
+    batch statistics) taken out of the comparison.  tape (NCHW): c0 the stem conv output, p0 the pooled stem output
+    (block 0's input), blocks[i] = c1, h1, c2, cd (a downsample block), out.
+      * every conv output is set to the tape's value, z + (v - z).detach(); the batch statistics are those of the
+        forced conv outputs (no running statistics are read or written);
+      * every ReLU output is z * [stored > 0] (h1, out: the recorded masks), then set to the stored value;
+      * the stem's full-resolution ReLU output is on no tape: the max-pool acts on relu(bn(c0 forced)) computed here
+        (torch routes a window's gradient to its first maximum), times [p0 > 0], set to p0;
+      * sd: the weights to differentiate (the caller rounds the conv weights to bf16); x takes its bf16-rounded value
+        here, its gradient passing straight through.
+    grad_round: a function applied (as an autograd hook) to the gradient of every activation the trunk's backward
+    stores -- c0, p0, c1, h1, c2, cd, out -- e.g. a rounding to bf16: the yardstick of a correct implementation with
+    those storage formats.  fault (tests only; FORCED_FAULTS_2D): a deliberately mis-wired graph -- "drop_identity"
+    layer1.1's identity branch passes no gradient, "drop_downsample" layer2.0's downsample branch passes none,
+    "mask_c2" the block-output masks are [c2 > 0], "pool_last" the max-pool gradient goes to a window's last maximum,
+    "unmasked_class00" layer1.1's output ReLU mask is not applied to the gradient at the (even, even) pixels (those a
+    stride-2 conv1 dgrad leaves to the 1x1 downsample dgrad above it)."""
+    assert fault is None or fault in FORCED_FAULTS_2D, fault
+    stem = prefix + ("conv1_a.weight" if modal == "audio" else "conv1.weight")
+    dt = sd[stem].dtype
+
+    def keep(t):
+        if grad_round is not None and t.requires_grad:
+            t.register_hook(grad_round)
+        return t
+
+    def force(z, v):
+        return keep(z + (v.to(dt) - z).detach())
+
+    def bn(c, name):
+        return F.batch_norm(c, None, None, sd[name + ".weight"], sd[name + ".bias"], True, 0.0, 1e-5)
+
+    x = x.to(dt)
+    x = x + (x.to(torch.bfloat16).to(dt) - x).detach()
+    c = force(F.conv2d(x, sd[stem], stride=2, padding=3), tape["c0"])
+    a = F.relu(bn(c, prefix + "bn1"))
+    pooled = _max_pool2d_last(a) if fault == "pool_last" else F.max_pool2d(a, 3, 2, 1)
+    x = force(pooled * (tape["p0"] > 0), tape["p0"])
+    blocks = iter(tape["blocks"])
+    for li, (planes, stride) in enumerate(STAGES, start=1):
+        for bi in range(2):
+            s = stride if bi == 0 else 1
+            p = f"{prefix}layer{li}.{bi}."
+            tb = next(blocks)
+            c1 = force(F.conv2d(x, sd[p + "conv1.weight"], stride=s, padding=1), tb["c1"])
+            h1 = force(bn(c1, p + "bn1") * (tb["h1"] > 0), tb["h1"])
+            c2 = force(F.conv2d(h1, sd[p + "conv2.weight"], stride=1, padding=1), tb["c2"])
+            z = bn(c2, p + "bn2")
+            if (p + "downsample.0.weight") in sd:
+                cd = force(F.conv2d(x, sd[p + "downsample.0.weight"], stride=s), tb["cd"])
+                idt = bn(cd, p + "downsample.1")
+                if fault == "drop_downsample" and (li, bi) == (2, 0):
+                    idt = idt.detach()
+            else:
+                idt = x.detach() if fault == "drop_identity" and (li, bi) == (1, 1) else x
+            mask = (tb["c2"] > 0) if fault == "mask_c2" else (tb["out"] > 0)
+            if fault == "unmasked_class00" and (li, bi) == (1, 1):
+                mask = mask.clone()
+                mask[:, :, ::2, ::2] = True
+            x = force((z + idt) * mask, tb["out"])
+    return x
+
+
+def resnet18_forced_grads(sd, x: torch.Tensor, modal: str, tape: dict, g_out: torch.Tensor,
+                          round_grads: bool = False, fault: str = None, prefix: str = None):
+    """{name without prefix: fp64 gradient} of (resnet18_forward_forced(...) * g_out).sum() on the CPU for every
+    trainable parameter of the trunk (the modal stem, the BN affine parameters, the block convs), plus "input": the
+    gradient of x at its bf16-rounded value.  Conv weights are the bf16-rounded parameters in fp64 (the gradient is
+    taken at them), BN parameters stay fp64.  prefix: the trunk's keys in sd (default by modal: "audnet." /
+    "imgnet.").  round_grads: every stored activation gradient is rounded to bf16 (the weight and input gradients
+    stay full sums)."""
+    if prefix is None:
+        prefix = "audnet." if modal == "audio" else "imgnet."
+    skip = ("conv1_flow.weight", "conv1.weight" if modal == "audio" else "conv1_a.weight")
+    names = [n for n, _, kind in resnet18_entries(prefix)
+             if kind in ("conv", "bn_w", "bn_b") and n[len(prefix):] not in skip]
+    s = {}
+    for n in names:
+        v = sd[n].detach()
+        v = v.to(torch.bfloat16) if v.dim() == 4 else v
+        s[n] = v.to(torch.float64).clone().requires_grad_(True)
+    xin = x.detach().to(torch.bfloat16).to(torch.float64).requires_grad_(True)
+    rnd = (lambda g: g.to(torch.bfloat16).to(g.dtype)) if round_grads else None
+    tape64 = {k: v.double() for k, v in tape.items() if k != "blocks"}
+    tape64["blocks"] = [{k: v.double() for k, v in tb.items()} for tb in tape["blocks"]]
+    feat = resnet18_forward_forced(s, prefix, xin, modal, tape64, grad_round=rnd, fault=fault)
+    assert feat.shape == g_out.shape, (feat.shape, g_out.shape)
+    (feat * g_out.double()).sum().backward()
+    # (a parameter a fault cuts off the graph has no gradient: zeros)
+    out = {n[len(prefix):]: (s[n].grad if s[n].grad is not None else torch.zeros_like(s[n])) for n in names}
+    out["input"] = xin.grad
+    return out
 
 
 def hardway_head(img_n: torch.Tensor, aud_n: torch.Tensor, epsilon=0.65, epsilon2=0.4, tau=0.03,
