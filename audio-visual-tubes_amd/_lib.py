@@ -113,6 +113,8 @@ SIGNATURES = {
     "avt_pack_video_stem_dgrad": (_I, [_P, _P, _P]),
     "avt_video_stem_dgrad": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "avt_bn_eval_bwd": (_I, [_P, _P, _P, _P, ctypes.POINTER(BnBwdTarget), ctypes.POINTER(BnBwdTarget), _P, _L, _I, _P]),
+    "avt_bn_eval_bwd_mask": (_I, [_P, _P, ctypes.POINTER(BnBwdTarget), ctypes.POINTER(BnBwdTarget), _L, _I, _P]),
+    "avt_stem_maxpool_bn_relu_eval_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "avt_pack3d_desc_bytes": (_Z, []),
     "avt_pack_conv3d_weights_batched": (_I, [_P, _I, _I, _I, _P]),
     "avt_pack_conv3d_weight": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),

@@ -589,7 +589,9 @@ constexpr int kStemLdsBytes = 48 * 1024;
 // per input row) and has twice the items in flight.  For input pixel (h, w) the candidate windows are
 // (p_h, q) with q = w/2 (kw = 1 if w even, 2 if odd) and, for odd w, q+1 (kw = 0); g' = [h0 > 0] * the
 // sum of gy over the candidates whose argmax is (h, w); gc = gamma*invstd*(g' - k1 - xhat*k2).
+// EVAL: the running-statistics rule gc = gamma*invstd*g' (mean / k1 / k2 are not read).
 constexpr int kStemBwdThreads = 512;
+template <bool EVAL>
 __global__ __launch_bounds__(kStemBwdThreads) void stem_maxpool_bn_bwd_apply_kernel(
     const bf16_t* __restrict__ gy, const unsigned char* __restrict__ idx, const bf16_t* __restrict__ c,
     const float* __restrict__ scale, const float* __restrict__ shift, const float* __restrict__ mean,
@@ -638,10 +640,10 @@ __global__ __launch_bounds__(kStemBwdThreads) void stem_maxpool_bn_bwd_apply_ker
     const int ch = c8 * 8 + e;
     k_sc[e] = scale[ch];
     k_sh[e] = shift[ch];
-    k_mu[e] = mean[ch];
     k_is[e] = invstd[ch];
-    k_k1[e] = k1[ch];
-    k_k2[e] = k2[ch];
+    k_mu[e] = EVAL ? 0.f : mean[ch];
+    k_k1[e] = EVAL ? 0.f : k1[ch];
+    k_k2[e] = EVAL ? 0.f : k2[ch];
     k_gi[e] = gamma[ch] * k_is[e];
   }
   // stage the (<= 2) pooled rows of gy and argmax: every load issued before any LDS store
@@ -700,8 +702,12 @@ __global__ __launch_bounds__(kStemBwdThreads) void stem_maxpool_bn_bwd_apply_ker
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
       gg[e] = __builtin_fmaf(xx[e], k_sc[e], k_sh[e]) > 0.f ? gg[e] : 0.f;
-      const float xh = (xx[e] - k_mu[e]) * k_is[e];
-      o[e] = k_gi[e] * (gg[e] - k_k1[e] - xh * k_k2[e]);
+      if (EVAL) {
+        o[e] = __builtin_fmaf(k_gi[e], gg[e], 0.f);  // (+ 0: a pixel with g' = 0 gets +0 whatever gamma's sign)
+      } else {
+        const float xh = (xx[e] - k_mu[e]) * k_is[e];
+        o[e] = k_gi[e] * (gg[e] - k_k1[e] - xh * k_k2[e]);
+      }
     }
     *reinterpret_cast<u32x4*>(gc + xo) = pack8(o);
   }
@@ -731,6 +737,7 @@ struct EvalBwdArgs {
   const bf16_t* y;      // mask y > 0, or
   const float* mscale;  // mask fma(xc, mscale, mshift) > 0 (xc of the first BN), or none
   const float* mshift;
+  const unsigned char* mk;  // BITS: mask = the [rows][C/8] bits of avt_bn_apply_mask
   bf16_t* gmask_out;    // optional g'
   const bf16_t* xc[2];
   const float* mean[2];
@@ -742,7 +749,7 @@ struct EvalBwdArgs {
   int C, rows_per_block;
 };
 
-template <bool TWO>
+template <bool TWO, bool BITS>
 __global__ __launch_bounds__(256) void bn_eval_bwd_kernel(EvalBwdArgs a) {
   __shared__ float red[2048 * 2];
   constexpr int NB = TWO ? 2 : 1;
@@ -768,7 +775,10 @@ __global__ __launch_bounds__(256) void bn_eval_bwd_kernel(EvalBwdArgs a) {
     float gg[8], xx[8], o[8];
     unpack8(reinterpret_cast<const u32x4*>(a.g)[off], gg);
     unpack8(reinterpret_cast<const u32x4*>(a.xc[0])[off], xx);
-    relu_mask8(gg, xx, a.y, off, a.mscale, a.mshift, c0);
+    if (BITS)
+      mask8(gg, a.mk[off]);
+    else
+      relu_mask8(gg, xx, a.y, off, a.mscale, a.mshift, c0);
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
       s1[e] += gg[e];
@@ -815,29 +825,19 @@ __global__ __launch_bounds__(256) void bn_eval_bwd_kernel(EvalBwdArgs a) {
 
 using namespace avt;
 
-// Eval-mode BatchNorm backward (see bn_eval_bwd_kernel).  t1 (and t2, sharing g') as avt_bn_bwd_mask's targets with
-// mean = running_mean and invstd = rsqrt(running_var + eps); a target's workspace is read only when its dgamma or
-// dbeta is non-NULL.  Mask: y (y > 0) if given, else (mscale, mshift) on t1's xc if given, else none.
-extern "C" int avt_bn_eval_bwd(const void* g, const void* y, const float* mscale, const float* mshift,
-                               const avt_bn_bwd_target* t1, const avt_bn_bwd_target* t2, void* gmask_out,
-                               long long rows, int C, void* stream) {
-  AVT_REQUIRE(g && t1, "bn_eval_bwd: null pointer");
-  AVT_REQUIRE((mscale == nullptr) == (mshift == nullptr), "bn_eval_bwd: mscale/mshift must be both set or both null");
-  AVT_REQUIRE(C % 8 == 0 && C <= 2048 && 256 % (C / 8) == 0, "bn_eval_bwd: C=%d unsupported", C);
-  AVT_REQUIRE(rows > 0, "bn_eval_bwd: empty input");
+// The launches of avt_bn_eval_bwd / avt_bn_eval_bwd_mask: a (mask fields set by the caller) gets the targets and the
+// row dealing of bn_bwd_reduce_launch; the pass, then a finalize per target whose dgamma or dbeta is wanted.
+static int bn_eval_bwd_launch(EvalBwdArgs& a, const avt_bn_bwd_target* t1, const avt_bn_bwd_target* t2, long long rows,
+                              int C, void* stream, const char* who) {
+  AVT_REQUIRE(C % 8 == 0 && C <= 2048 && 256 % (C / 8) == 0, "%s: C=%d unsupported", who, C);
+  AVT_REQUIRE(rows > 0, "%s: empty input", who);
   const avt_bn_bwd_target* ts[2] = {t1, t2};
-  EvalBwdArgs a{};
-  a.g = (const bf16_t*)g;
-  a.y = (const bf16_t*)y;
-  a.mscale = y ? nullptr : mscale;
-  a.mshift = y ? nullptr : mshift;
-  a.gmask_out = (bf16_t*)gmask_out;
   for (int k = 0; k < (t2 ? 2 : 1); ++k) {
     const avt_bn_bwd_target* t = ts[k];
-    AVT_REQUIRE(t->xc && t->mean && t->invstd && t->gamma && t->gc, "bn_eval_bwd: null target pointer");
+    AVT_REQUIRE(t->xc && t->mean && t->invstd && t->gamma && t->gc, "%s: null target pointer", who);
     const bool wants = t->dgamma || t->dbeta;
     AVT_REQUIRE(!wants || (t->workspace && ((uintptr_t)t->workspace & 7) == 0),
-                "bn_eval_bwd: dgamma/dbeta need an 8-byte aligned workspace");
+                "%s: dgamma/dbeta need an 8-byte aligned workspace", who);
     a.xc[k] = (const bf16_t*)t->xc;
     a.mean[k] = t->mean;
     a.invstd[k] = t->invstd;
@@ -854,17 +854,53 @@ extern "C" int avt_bn_eval_bwd(const void* g, const void* y, const float* mscale
   a.rows_per_block = (int)rpb;
   const int nblk = (int)((rows + rpb - 1) / rpb);
   hipStream_t st = (hipStream_t)stream;
-  if (t2)
-    hipLaunchKernelGGL(bn_eval_bwd_kernel<true>, dim3(nblk), dim3(256), 0, st, a);
-  else
-    hipLaunchKernelGGL(bn_eval_bwd_kernel<false>, dim3(nblk), dim3(256), 0, st, a);
+  if (a.mk) {
+    if (t2)
+      hipLaunchKernelGGL((bn_eval_bwd_kernel<true, true>), dim3(nblk), dim3(256), 0, st, a);
+    else
+      hipLaunchKernelGGL((bn_eval_bwd_kernel<false, true>), dim3(nblk), dim3(256), 0, st, a);
+  } else {
+    if (t2)
+      hipLaunchKernelGGL((bn_eval_bwd_kernel<true, false>), dim3(nblk), dim3(256), 0, st, a);
+    else
+      hipLaunchKernelGGL((bn_eval_bwd_kernel<false, false>), dim3(nblk), dim3(256), 0, st, a);
+  }
   for (int k = 0; k < (t2 ? 2 : 1); ++k) {
     if (!a.acc[k]) continue;
     float* k1 = (float*)(a.acc[k] + kBnHdr);  // (the train-mode rule's means: written, not used here)
     hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + kFinCB - 1) / kFinCB), dim3(kFinThreads), 0, st, a.acc[k], C,
                        1.0 / (double)rows, ts[k]->dgamma, ts[k]->dbeta, k1, k1 + C);
   }
-  return check_launch("bn_eval_bwd");
+  return check_launch(who);
+}
+
+// Eval-mode BatchNorm backward (see bn_eval_bwd_kernel).  t1 (and t2, sharing g') as avt_bn_bwd_mask's targets with
+// mean = running_mean and invstd = rsqrt(running_var + eps); a target's workspace is read only when its dgamma or
+// dbeta is non-NULL.  Mask: y (y > 0) if given, else (mscale, mshift) on t1's xc if given, else none.
+extern "C" int avt_bn_eval_bwd(const void* g, const void* y, const float* mscale, const float* mshift,
+                               const avt_bn_bwd_target* t1, const avt_bn_bwd_target* t2, void* gmask_out,
+                               long long rows, int C, void* stream) {
+  AVT_REQUIRE(g && t1, "bn_eval_bwd: null pointer");
+  AVT_REQUIRE((mscale == nullptr) == (mshift == nullptr), "bn_eval_bwd: mscale/mshift must be both set or both null");
+  EvalBwdArgs a{};
+  a.g = (const bf16_t*)g;
+  a.y = (const bf16_t*)y;
+  a.mscale = y ? nullptr : mscale;
+  a.mshift = y ? nullptr : mshift;
+  a.gmask_out = (bf16_t*)gmask_out;
+  return bn_eval_bwd_launch(a, t1, t2, rows, C, stream, "bn_eval_bwd");
+}
+
+// avt_bn_eval_bwd with the mask read from the bits of avt_bn_apply_mask (a 2-D block output: 1/16 of the bytes of
+// the stored output).  The same kernel body, row dealing and slot order: where the bits are [out > 0] the results are
+// those of avt_bn_eval_bwd(y = out) bit for bit.
+extern "C" int avt_bn_eval_bwd_mask(const void* g, const void* mask, const avt_bn_bwd_target* t1,
+                                    const avt_bn_bwd_target* t2, long long rows, int C, void* stream) {
+  AVT_REQUIRE(g && mask && t1, "bn_eval_bwd_mask: null pointer");
+  EvalBwdArgs a{};
+  a.g = (const bf16_t*)g;
+  a.mk = (const unsigned char*)mask;
+  return bn_eval_bwd_launch(a, t1, t2, rows, C, stream, "bn_eval_bwd_mask");
 }
 
 extern "C" size_t avt_bn_acc_doubles(long long rows, int C) {
@@ -1126,9 +1162,41 @@ extern "C" int avt_stem_maxpool_bn_relu_bwd(const void* gy, const void* idx, con
                      1.0 / ((double)N * H * W), dgamma, dbeta, k1, k2);
   if (!diag_skip(2, st)) hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + kFinCB - 1) / kFinCB), dim3(kFinThreads), 0, st, acc, C,
                      1.0 / ((double)N * H * W), dgamma, dbeta, k1, k2);
-  hipLaunchKernelGGL(stem_maxpool_bn_bwd_apply_kernel, dim3(N * ((H + 1) / 2)), dim3(kStemBwdThreads), (size_t)6 * Q * C,
-                     st, (const bf16_t*)gy,
+  hipLaunchKernelGGL(stem_maxpool_bn_bwd_apply_kernel<false>, dim3(N * ((H + 1) / 2)), dim3(kStemBwdThreads),
+                     (size_t)6 * Q * C, st, (const bf16_t*)gy,
                      (const unsigned char*)idx, (const bf16_t*)c, scale, shift, mean, invstd, gamma, k1, k2,
                      (bf16_t*)gc, H, W, C, ilog2(C / 8), P, Q);
   return check_launch("stem_maxpool_bn_relu_bwd");
+}
+
+// Eval-mode (running-statistics) stem backward: one pass gc = gamma*invstd * [fma(c, scale, shift) > 0] * (the gy of the
+// windows whose argmax is the pixel).  dgamma / dbeta (optional) are summed over the pooled rows from (gy, carg) -- the
+// train-mode entry's reduce -- through the fixed-order slots and added into the gradient by the finalize; both NULL:
+// no workspace, nothing reduced.
+extern "C" int avt_stem_maxpool_bn_relu_eval_bwd(const void* gy, const void* idx, const void* carg, const void* c,
+                                                 const float* scale, const float* shift, const float* mean,
+                                                 const float* invstd, const float* gamma, float* dgamma, float* dbeta,
+                                                 void* gc, void* workspace, int N, int H, int W, int C, void* stream) {
+  AVT_REQUIRE(gy && idx && c && scale && shift && invstd && gamma && gc, "stem_maxpool_bn_relu_eval_bwd: null pointer");
+  AVT_REQUIRE(C % 8 == 0 && C <= 2048 && 256 % (C / 8) == 0, "stem_maxpool_bn_relu_eval_bwd: C=%d unsupported", C);
+  AVT_REQUIRE((long long)((W + 1) / 2 + 1) * C * 6 <= kStemLdsBytes && (long long)2 * W * (C / 8) <= 6 * kStemBwdThreads,
+              "stem_maxpool_bn_relu_eval_bwd: W=%d C=%d too wide", W, C);
+  AVT_REQUIRE(N > 0 && H > 0 && W > 0, "stem_maxpool_bn_relu_eval_bwd: empty input");
+  const bool wants = dgamma || dbeta;
+  AVT_REQUIRE(!wants || (carg && mean && workspace && ((uintptr_t)workspace & 7) == 0),
+              "stem_maxpool_bn_relu_eval_bwd: dgamma/dbeta need carg, mean and an 8-byte aligned workspace");
+  const int P = (H + 2 - 3) / 2 + 1, Q = (W + 2 - 3) / 2 + 1;
+  hipStream_t st = (hipStream_t)stream;
+  if (wants) {
+    double* acc = (double*)workspace;
+    float* k1 = (float*)(acc + kBnHdr);  // (the train-mode rule's means: written, not used here)
+    bn_bwd_reduce_launch((const bf16_t*)gy, nullptr, scale, shift, (const bf16_t*)carg, mean, invstd, acc,
+                         (long long)N * P * Q, C, st);
+    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + kFinCB - 1) / kFinCB), dim3(kFinThreads), 0, st, acc, C,
+                       1.0 / ((double)N * H * W), dgamma, dbeta, k1, k1 + C);
+  }
+  hipLaunchKernelGGL(stem_maxpool_bn_bwd_apply_kernel<true>, dim3(N * ((H + 1) / 2)), dim3(kStemBwdThreads),
+                     (size_t)6 * Q * C, st, (const bf16_t*)gy, (const unsigned char*)idx, (const bf16_t*)c, scale, shift,
+                     nullptr, invstd, gamma, nullptr, nullptr, (bf16_t*)gc, H, W, C, ilog2(C / 8), P, Q);
+  return check_launch("stem_maxpool_bn_relu_eval_bwd");
 }

@@ -422,8 +422,9 @@ class AVEngine:
         return y
 
     def forward(self, image: torch.Tensor, audio: torch.Tensor, training: bool, with_ce: bool = False,
-                ce_scale: float = 1.0, layer_io: bool = False, vision_pre=None):
-        """layer_io: also return each trunk's layer4 input/output ("v_in"/"v", "a_in"/"a", NHWC bf16)
+                ce_scale: float = 1.0, layer_io: bool = False, vision_pre=None, tape: bool = False):
+        """tape (with training=False): keep the tape of the eval forward for the running-statistics backward
+        (Trunk.forward; backward() reads the rule from the tape).  layer_io: also return each trunk's layer4 input/output ("v_in"/"v", "a_in"/"a", NHWC bf16)
         for forward hooks registered on imgnet.layer4 / audnet.layer4 (test.py:63).  vision_pre():
         launches issued at the head of the vision trunk's branch (ordered before the head, concurrent
         with the audio trunk)."""
@@ -444,6 +445,7 @@ class AVEngine:
         # counters and vision_pre() (e.g. the gradient zeroing of the step) run on the vision branch -- the
         # shorter trunk's slack, not the serial section
         dev = image.device
+        keep = training or tape
 
         io_a = {} if layer_io else None
         io_v = {} if layer_io else None
@@ -452,7 +454,7 @@ class AVEngine:
             if split_pack:
                 self.pack_trunk(self.aud, 1)
             xa = self._to_nhwc(audio, 1)
-            a, tape_a = yield from self.aud.forward_iter(xa, self.store, training, io_a)
+            a, tape_a = yield from self.aud.forward_iter(xa, self.store, training, io_a, tape)
             C = a.shape[-1]
             an = torch.empty(B, C, device=dev, dtype=torch.float32)
             amax = torch.empty(B, C, device=dev, dtype=torch.int32)
@@ -469,8 +471,8 @@ class AVEngine:
             if split_pack:
                 self.pack_trunk(self.img, 1)
             xi = self._to_nhwc(image, 4)
-            out = yield from self.img.forward_iter(xi, self.store, training, io_v)
-            if split_pack and training:
+            out = yield from self.img.forward_iter(xi, self.store, training, io_v, tape)
+            if split_pack and keep:
                 self.pack_trunk(self.img, 2)
                 self.pack_trunk(self.aud, 2)
             return out
@@ -496,7 +498,7 @@ class AVEngine:
         if layer_io:
             out.update(v_in=io_v["layer4_in"], a=a, a_in=io_a["layer4_in"])
         tape = None
-        if training:
+        if keep:
             tape = {"img": tape_i, "aud": tape_a, "v": v, "a": a, "an": an, "amax": amax, "anorm": anorm,
                     "inv": inv, "vsum": vsum, "A0": A0, "save": save, "B": B, "P": Pn, "C": C}
         if with_ce:
@@ -559,7 +561,8 @@ class AVEngine:
 
     def backward(self, tape, dlogits: Optional[torch.Tensor], gflat: torch.Tensor, on_boundary=None,
                  dwA: Optional[torch.Tensor] = None, dA=None, dPos=None, dNeg=None, on_trunk_end=None):
-        """Accumulate d(loss)/d(params) into gflat[:n_train] (caller zeroes it).
+        """Accumulate d(loss)/d(params) into gflat[:n_train] (caller zeroes it).  gflat None: only for an eval
+        tape whose trunks are both marked "frozen" (input gradients only: no parameter gradient is computed).
         dwA: upstream gradient of weighted_A (the 16-frame losses, train_hardway.py:138-141); dA/dPos/dNeg:
         of the returned maps.  The two trunks' backward runs concurrently (audio on the side stream) in
         two segments: layer4+layer3 of both, then layer2..stem of both.  on_boundary(tags) is called
@@ -572,7 +575,7 @@ class AVEngine:
         gv, gan = self.head_backward(tape, dlogits, dwA, dA=dA, dPos=dPos, dNeg=dNeg)
         a = tape["a"]
         B, C = tape["B"], tape["C"]
-        self.store.grads = self.flat.grad_views(gflat)
+        self.store.grads = None if gflat is None else self.flat.grad_views(gflat)
         hi = self.img.HI_BLOCK
         seg = on_boundary is not None  # two segments (joined at the boundary) only when someone listens
         aud, img, ta, ti = self.aud, self.img, tape["aud"], tape["img"]
@@ -634,7 +637,8 @@ class TrunkEngine(AVEngine):
         self.trunks2d = [self.trunk]
         self.bn_trunks = [self.trunk]
 
-    def forward(self, x: torch.Tensor, training: bool):
+    def forward(self, x: torch.Tensor, training: bool, tape: bool = False):
+        """tape (with training=False): keep the eval forward's tape (Trunk.forward)."""
         if not x.is_cuda:
             raise RuntimeError("avt: inputs must be on the GPU (no CPU path)")
         cin = 1 if self._modal == "audio" else 3
@@ -644,7 +648,7 @@ class TrunkEngine(AVEngine):
         if training:
             self.flat.nbt.index_add_(0, self._nbt_idx, torch.ones_like(self._nbt_idx))
         xin = self._to_nhwc(x, self.trunk.stem.cp)
-        y, tape = self.trunk.forward(xin, self.store, training)
+        y, tape = self.trunk.forward(xin, self.store, training, tape=tape)
         N, h, w, C = y.shape
         out = torch.empty(N, C, h, w, device=x.device, dtype=torch.float32)
         call("avt_nhwc_bf16_to_nchw", P(y), P(out), N, C, h * w, stream_ptr())
@@ -652,9 +656,9 @@ class TrunkEngine(AVEngine):
 
     def backward(self, tape, g_out: torch.Tensor, gflat: torch.Tensor):
         """g_out [N,512,h,w] fp32 (any layout) -> parameter gradients accumulated into gflat; returns the input
-        gradient [N,Cin,H,W] fp32 when tape["want_dx"] was set, else None."""
+        gradient [N,Cin,H,W] fp32 when tape["want_dx"] was set, else None.  gflat None: a "frozen" eval tape."""
         g = g_out.permute(0, 2, 3, 1).to(torch.bfloat16).contiguous()  # layout plumbing
-        self.store.grads = self.flat.grad_views(gflat)
+        self.store.grads = None if gflat is None else self.flat.grad_views(gflat)
         try:
             self.trunk.backward(tape, g, self.store, None)
         finally:

@@ -70,6 +70,20 @@ class ResNet(nn.Module):
         # it here would turn the parameters into channels_last views before an enclosing AVENet re-inits
         # them (model.py:104-110), and normal_ fills a channels_last view in another element order
         self._own_flat = None
+        self._avt_eval_backward = False  # enable_eval_backward(): eval-mode (running-statistics BN) backward
+
+    def enable_eval_backward(self):
+        """Opt in to gradients through this trunk in eval mode: BatchNorm is differentiated as the affine map of
+        its running statistics (read, never updated), with gradients into the parameters that require grad and
+        into ``x`` when it requires grad.  Idempotent; returns self.  A trunk owned by an AVENet follows its
+        parent's flag (``AVENet.enable_eval_backward``)."""
+        self._avt_eval_backward = True
+        return self
+
+    def _eval_backward(self) -> bool:
+        if self._avt_parent is not None and self._avt_parent[0]() is not None:
+            return bool(getattr(self._avt_parent[0](), "_avt_eval_backward", False))
+        return bool(getattr(self, "_avt_eval_backward", False))
 
     def _make_layer(self, planes, blocks, stride):
         downsample = None
@@ -132,21 +146,24 @@ class ResNet(nn.Module):
 
     def forward(self, x):
         eng, flat, names, params = self._engine_and_params()
-        need_grad = torch.is_grad_enabled() and (x.requires_grad or (self.training and any(p.requires_grad for p in params)))
-        if need_grad and not self.training:
+        eval_bwd = not self.training and self._eval_backward()
+        need_grad = torch.is_grad_enabled() and (
+            x.requires_grad or ((self.training or eval_bwd) and any(p.requires_grad for p in params)))
+        if need_grad and not self.training and not eval_bwd:
             raise NotImplementedError("avt: gradients through an eval-mode trunk are not computed (train-mode "
                                       "BatchNorm only)")
         if need_grad:
-            return _TrunkFunction.apply(eng, names, x, *params)
+            return _TrunkFunction.apply(eng, names, self.training, x, *params)
         out, _ = eng.forward(x, self.training)
         return out
 
 
 class _TrunkFunction(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, engine, names, x, *params):
-        out, tape = engine.forward(x, True)
-        tape["want_dx"] = ctx.needs_input_grad[2]  # d(loss)/d(x) through the 7x7 stem (avt_conv_stem_dgrad)
+    def forward(ctx, engine, names, training, x, *params):
+        out, tape = engine.forward(x, training, tape=True)  # (eval mode: the running-statistics tape)
+        tape["want_dx"] = ctx.needs_input_grad[3]  # d(loss)/d(x) through the 7x7 stem (avt_conv_stem_dgrad)
+        tape["frozen"] = not any(ctx.needs_input_grad[4:])  # eval tape: input gradient only, no wgrad / BN sums
         ctx.engine, ctx.tape, ctx.names = engine, tape, names
         ctx.set_materialize_grads(False)
         return out
@@ -154,15 +171,19 @@ class _TrunkFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         if g is None:
-            return (None, None, None) + (None,) * len(ctx.names)
+            return (None, None, None, None) + (None,) * len(ctx.names)
         if ctx.tape is None:
             raise RuntimeError("avt: second backward through a trunk forward")
         flat = ctx.engine.flat
+        if not ctx.tape["training"] and ctx.tape["frozen"]:
+            gx = ctx.engine.backward(ctx.tape, g, None)
+            ctx.tape = None
+            return (None, None, None, gx) + (None,) * len(ctx.names)
         gflat = torch.zeros(flat.n_train, device=g.device, dtype=torch.float32)
         gx = ctx.engine.backward(ctx.tape, g, gflat)
         ctx.tape = None
         views = flat.param_grad_views(gflat)
-        return (None, None, gx) + tuple(views[n] for n in ctx.names)
+        return (None, None, None, gx) + tuple(views[n] for n in ctx.names)
 
 
 class HardWayArgs:
@@ -230,12 +251,14 @@ def _run_forward_hooks(module: nn.Module, inp: torch.Tensor, out: torch.Tensor):
 class _AVENetFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, engine: AVEngine, training: bool, sink: Optional[dict], image, audio, *params):
-        out, tape = engine.forward(image, audio, training, layer_io=sink is not None)
+        out, tape = engine.forward(image, audio, training, layer_io=sink is not None, tape=True)
         if sink is not None:
             sink.update(out)
         if tape is not None:  # d(loss)/d(frames, spectrogram) through the 7x7 stems when the inputs require it
             tape["img"]["want_dx"] = ctx.needs_input_grad[3]
             tape["aud"]["want_dx"] = ctx.needs_input_grad[4]
+            # eval tape with no parameter among the inputs requiring grad: input gradients only (no wgrad / BN sums)
+            tape["img"]["frozen"] = tape["aud"]["frozen"] = not any(ctx.needs_input_grad[5:])
         ctx.engine = engine
         ctx.tape = tape
         ctx.n_params = len(params)
@@ -252,10 +275,13 @@ class _AVENetFunction(torch.autograd.Function):
             return (None,) * 5 + (None,) * nparams
         flat = engine.flat
         dev = next(g for g in (glogits, gwA, gA, gPos, gNeg) if g is not None).device
-        gflat = torch.zeros(flat.n_train, device=dev, dtype=torch.float32)
+        frozen = not ctx.tape["img"]["training"] and ctx.tape["img"]["frozen"]
+        gflat = None if frozen else torch.zeros(flat.n_train, device=dev, dtype=torch.float32)
         engine.backward(ctx.tape, glogits, gflat, dwA=gwA, dA=gA, dPos=gPos, dNeg=gNeg)
         gimg, gaud = ctx.tape["img"].get("dx"), ctx.tape["aud"].get("dx")
         ctx.tape = None
+        if frozen:
+            return (None, None, None, gimg, gaud) + (None,) * nparams
         views = flat.param_grad_views(gflat)
         grads = tuple(views.get(n) for n in flat.pnames[:nparams])
         return (None, None, None, gimg, gaud) + grads
@@ -286,8 +312,19 @@ class AVENet(nn.Module):
         # other GPUs, one over a mirror of the flat store there.  A dict, so that replicas (which get a
         # shallow copy of this __dict__) create and find them in the model's cache.
         self._engines = {}
+        self._avt_eval_backward = False  # enable_eval_backward(): eval-mode (running-statistics BN) backward
         for prefix, net in (("imgnet.", self.imgnet), ("audnet.", self.audnet)):
             net._adopt(self, prefix)
+
+    def enable_eval_backward(self):
+        """Opt in to gradients through the model in eval mode (``model.eval()``: test.py:85, visualize.py:121):
+        BatchNorm is differentiated as the affine map of its running statistics, which are read and never
+        updated.  Gradients flow from all five outputs into the parameters that require grad and into ``image``
+        / ``audio`` when they require grad -- saliency at the evaluated operating point, fine-tuning with frozen
+        BatchNorm.  With every parameter frozen only the input gradients are computed (no wgrad launch).
+        Idempotent; returns self; the trunks (``model.imgnet(x)``) follow this flag; train mode is unchanged."""
+        self._avt_eval_backward = True
+        return self
 
     def __getstate__(self):
         state = self.__dict__.copy()
@@ -359,15 +396,17 @@ class AVENet(nn.Module):
         hooked = [(n, m) for n, m in (("imgnet", self.imgnet.layer4), ("audnet", self.audnet.layer4))
                   if m._forward_hooks]
         sink = {} if hooked else None
-        if torch.is_grad_enabled() and not self.training and (image.requires_grad or audio.requires_grad):
+        eval_bwd = not self.training and getattr(self, "_avt_eval_backward", False)
+        if torch.is_grad_enabled() and not self.training and not eval_bwd and (
+                image.requires_grad or audio.requires_grad):
             # as ResNet.forward: an input gradient through eval-mode BatchNorm is not computed -- refuse here rather
             # than return detached outputs whose backward() fails far from the cause
             raise NotImplementedError("avt: gradients through an eval-mode AVENet are not computed (train-mode "
                                       "BatchNorm only)")
-        need_grad = torch.is_grad_enabled() and self.training and (
+        need_grad = torch.is_grad_enabled() and (self.training or eval_bwd) and (
             image.requires_grad or audio.requires_grad or any(p.requires_grad for p in train_params))
         if need_grad:
-            A, logits, wA, Pos, Neg = _AVENetFunction.apply(eng, True, sink, image, audio, *train_params)
+            A, logits, wA, Pos, Neg = _AVENetFunction.apply(eng, self.training, sink, image, audio, *train_params)
         else:
             out, _ = eng.forward(image, audio, self.training, layer_io=sink is not None)
             A, logits, wA, Pos, Neg = out["A"], out["logits"], out["weighted_A"], out["Pos"], out["Neg"]

@@ -250,16 +250,22 @@ class Trunk:
         stats = _bn_finalize(y, acc, N * Pq * Qq, bn, store, training, momentum=self.bn_momentum, rep=self.bn_rep)
         return y, stats, Pq, Qq
 
-    def forward(self, x: torch.Tensor, store: Store, training: bool, io: Optional[Dict] = None):
+    def forward(self, x: torch.Tensor, store: Store, training: bool, io: Optional[Dict] = None, tape: bool = False):
         """x: [N,H,W,cp] bf16 NHWC. Returns (layer4 map [N,h,w,512] bf16, tape).  io (optional) receives
-        "layer4_in": the layer3 output [N,h,w,256] (the input a forward hook on .layer4 sees)."""
-        return drive(self.forward_iter(x, store, training, io))
+        "layer4_in": the layer3 output [N,h,w,256] (the input a forward hook on .layer4 sees).
+        tape (eval mode only; a train-mode forward always keeps its tape): keep the tape of an eval forward for
+        the running-statistics backward -- the block outputs then go through avt_bn_apply_mask (the same fma,
+        the same bits of out), `stats` are the running-statistics (scale, shift, mean, invstd); no accumulator
+        is allocated and no running statistic is touched."""
+        return drive(self.forward_iter(x, store, training, io, tape))
 
-    def forward_iter(self, x: torch.Tensor, store: Store, training: bool, io: Optional[Dict] = None):
+    def forward_iter(self, x: torch.Tensor, store: Store, training: bool, io: Optional[Dict] = None,
+                     tape: bool = False):
         """forward() as a generator that yields after each launch group, so that two trunks' launches can
         be issued interleaved on two streams (engine._interleave); returns forward()'s result."""
         N, H, W, _ = x.shape
-        tape: Dict = {"x": x, "N": N, "H": H, "W": W, "blocks": []}
+        keep = training or tape
+        tape: Dict = {"x": x, "N": N, "H": H, "W": W, "blocks": [], "training": training}
         c0, st0, H1, W1 = self._conv_bn(x, N, H, W, self.stem, self.bn1, store, training)
         yield
         # bn1 -> relu -> maxpool fused: the full-resolution relu(bn1(c0)) is never stored
@@ -288,9 +294,9 @@ class Trunk:
             c2, s2, _, _ = self._conv_bn(h1, N, Ho, Wo, blk["conv2"], blk["bn2"], store, training)
             yield
             out = torch.empty_like(c2)
-            # training: the output's ReLU mask as bits ([rows][C/8] u8) for the backward, which then never
+            # with a tape: the output's ReLU mask as bits ([rows][C/8] u8) for the backward, which then never
             # re-reads `out` (1/16 of its bytes)
-            om = torch.empty(c2.numel() // 8, device=x.device, dtype=torch.uint8) if training else None
+            om = torch.empty(c2.numel() // 8, device=x.device, dtype=torch.uint8) if keep else None
             if blk["down"] is not None:
                 cd, sd, _, _ = self._conv_bn(cur, N, Hc, Wc, blk["down"], blk["bnd"], store, training)
                 yield
@@ -298,7 +304,7 @@ class Trunk:
                 t.update(cd=cd, sd=sd)
             else:
                 res = (P(cur), None, None)
-            if training:
+            if keep:
                 call("avt_bn_apply_mask", P(c2), P(s2[0]), P(s2[1]), *res, P(out), P(om), N * Ho * Wo, c2.shape[-1],
                      stream_ptr())
             else:
@@ -308,7 +314,7 @@ class Trunk:
             tape["blocks"].append(t)
             yield
             cur, Hc, Wc = out, Ho, Wo
-        if not training:
+        if not keep:
             tape = None
         return cur, tape
 
@@ -322,18 +328,36 @@ class Trunk:
              rows, bn.c, stream_ptr())
         return gc
 
-    def _target(self, xc, stats, bn: BNSpec, store: Store) -> BnBwdTarget:
+    def _target(self, xc, stats, bn: BNSpec, store: Store, pgrad: bool = True) -> BnBwdTarget:
+        """pgrad=False (eval backward with frozen parameters): no dgamma / dbeta, no workspace."""
         t = BnBwdTarget()
         gc = torch.empty_like(xc)
         t.xc, t.mean, t.invstd = xc.data_ptr(), stats[2].data_ptr(), stats[3].data_ptr()
         t.gamma = store.param(bn.prefix + ".weight").data_ptr()
-        dg, db = store.grad(bn.prefix + ".weight"), store.grad(bn.prefix + ".bias")
-        t.dgamma = dg.data_ptr() if dg is not None else None
-        t.dbeta = db.data_ptr() if db is not None else None
+        if pgrad:
+            dg, db = store.grad(bn.prefix + ".weight"), store.grad(bn.prefix + ".bias")
+            t.dgamma = dg.data_ptr() if dg is not None else None
+            t.dbeta = db.data_ptr() if db is not None else None
+            t.workspace = store.stat_acc(bn, "bwd", xc.numel() // bn.c).data_ptr()
         t.gc = gc.data_ptr()
-        t.workspace = store.stat_acc(bn, "bwd", xc.numel() // bn.c).data_ptr()
         t.keep = gc  # the output tensor (ctypes.Structure keeps no reference)
         return t
+
+    def _bn_eval_bwd_mask(self, g, mask, xc, stats, bn: BNSpec, store: Store, pgrad: bool, xc2=None, stats2=None,
+                          bn2=None):
+        """_bn_bwd_mask under running statistics (avt_bn_eval_bwd_mask): one pass, gc = gamma*invstd*g*bit."""
+        t1 = self._target(xc, stats, bn, store, pgrad)
+        t2 = self._target(xc2, stats2, bn2, store, pgrad) if bn2 is not None else None
+        call("avt_bn_eval_bwd_mask", P(g), P(mask), ctypes.byref(t1), ctypes.byref(t2) if t2 is not None else None,
+             xc.numel() // bn.c, bn.c, stream_ptr())
+        return t1.keep, (t2.keep if t2 is not None else None)
+
+    def _bn_eval_relu_bwd(self, g, xc, stats, bn: BNSpec, store: Store, pgrad: bool):
+        """_bn_relu_bwd under running statistics (avt_bn_eval_bwd, mask recomputed from (xc, scale, shift))."""
+        t1 = self._target(xc, stats, bn, store, pgrad)
+        call("avt_bn_eval_bwd", P(g), None, P(stats[0]), P(stats[1]), ctypes.byref(t1), None, None,
+             xc.numel() // bn.c, bn.c, stream_ptr())
+        return t1.keep
 
     def _bn_bwd_mask(self, g, mask, xc, stats, bn: BNSpec, store: Store, xc2=None, stats2=None, bn2=None):
         """Block-output BN backward(s) from the ReLU mask bits: bn2 alone, or bn2 + downsample.1 in one
@@ -451,8 +475,15 @@ class Trunk:
         block lo's input, premasked): with premasked the gradient is already multiplied by block lo-1's
         output ReLU mask and that block's bn2 (+ downsample BN) reductions are accumulated -- each dgrad
         that produces a BN's input gradient carries the BN-backward epilogue (avt_conv2d_dgrad_bn), so
-        the standalone reduction pass runs only where the gradient enters a trunk (from the head)."""
+        the standalone reduction pass runs only where the gradient enters a trunk (from the head).
+        A tape of an eval forward (tape["training"] False) takes the running-statistics rule: block outputs through
+        avt_bn_eval_bwd_mask, bn1 + ReLU through avt_bn_eval_bwd, always unfused (the dgrad epilogues accumulate
+        batch-statistics sums that rule does not use), the same dgrads and wgrads; with tape["frozen"] (no trunk
+        parameter wants a gradient) no wgrad is launched and no BN sum is reduced."""
         N = tape["N"]
+        ev = not tape.get("training", True)
+        pgrad = not (ev and tape.get("frozen", False))
+        fuse = FUSE_BN_BWD and not ev
         for bi in reversed(range(lo, hi)):
             blk, t = self.blocks[bi], tape["blocks"][bi]
             Hc, Wc, Ho, Wo = t["H"], t["W"], t["Ho"], t["Wo"]
@@ -464,7 +495,10 @@ class Trunk:
             else:  # g' = g * [out > 0] from the forward's mask bits; an identity block's residual gradient
                 # enters the conv1 dgrad below as (g, mask) instead of a stored g'
                 gres = None
-                if identity and FUSE_BN_BWD and bi > 0:  # conv1's dgrad below carries a BN epilogue: store g'
+                if ev:
+                    g_c2, g_cd = self._bn_eval_bwd_mask(g, t["om"], t["c2"], t["s2"], blk["bn2"], store, pgrad,
+                                                        *(() if identity else (t["cd"], t["sd"], blk["bnd"])))
+                elif identity and fuse and bi > 0:  # conv1's dgrad below carries a BN epilogue: store g'
                     gres = torch.empty_like(t["c2"])
                     g_c2 = self._bn_bwd(g, t["out"], t["c2"], t["s2"], blk["bn2"], store, gmask_out=gres)
                     g_cd = None
@@ -474,24 +508,29 @@ class Trunk:
                     g_c2, g_cd = self._bn_bwd_mask(g, t["om"], t["c2"], t["s2"], blk["bn2"], store,
                                                    t["cd"], t["sd"], blk["bnd"])
             yield
-            self._wgrad(t["h1"], g_c2, N, Ho, Wo, blk["conv2"], store)
+            if pgrad:
+                self._wgrad(t["h1"], g_c2, N, Ho, Wo, blk["conv2"], store)
             yield
-            if FUSE_BN_BWD:  # conv2 dgrad with bn1's backward (ReLU mask from its pre-activation) in the epilogue
+            if fuse:  # conv2 dgrad with bn1's backward (ReLU mask from its pre-activation) in the epilogue
                 g_h1 = self._dgrad(g_c2, N, Ho, Wo, blk["conv2"], store,
                                    epi=self._epi(store, blk["bn1"], t["c1"], t["s1"]))
                 g_c1 = self._bn_bwd_premasked(g_h1, t["c1"], t["s1"], blk["bn1"], store)
             else:
                 g_h1 = self._dgrad(g_c2, N, Ho, Wo, blk["conv2"], store)
                 yield
-                g_c1 = self._bn_relu_bwd(g_h1, t["c1"], t["s1"], blk["bn1"], store)
+                if ev:
+                    g_c1 = self._bn_eval_relu_bwd(g_h1, t["c1"], t["s1"], blk["bn1"], store, pgrad)
+                else:
+                    g_c1 = self._bn_relu_bwd(g_h1, t["c1"], t["s1"], blk["bn1"], store)
             yield
-            self._wgrad(t["x"], g_c1, N, Hc, Wc, blk["conv1"], store)
-            yield
-            if not identity:
-                self._wgrad(t["x"], g_cd, N, Hc, Wc, blk["down"], store)
+            if pgrad:
+                self._wgrad(t["x"], g_c1, N, Hc, Wc, blk["conv1"], store)
                 yield
+                if not identity:
+                    self._wgrad(t["x"], g_cd, N, Hc, Wc, blk["down"], store)
+                    yield
             epi = None
-            if bi > 0 and FUSE_BN_BWD:  # the next block down: its bn2 (+ downsample BN) backward rides on this dgrad
+            if bi > 0 and fuse:  # the next block down: its bn2 (+ downsample BN) backward rides on this dgrad
                 pb, pt = self.blocks[bi - 1], tape["blocks"][bi - 1]
                 has_d = pb["down"] is not None
                 mk = lambda skip00, append=False: self._epi(
@@ -525,6 +564,20 @@ class Trunk:
         H1, W1 = tape["H1"], tape["W1"]
         c0, st0 = tape["c0"], tape["st0"]
         g_c0 = torch.empty_like(c0)
+        ev = not tape.get("training", True)
+        pgrad = not (ev and tape.get("frozen", False))
+        if ev:  # running statistics: one scatter pass (+ the pooled-row sums when bn1's gradients are wanted)
+            gn = self.bn1.prefix
+            call("avt_stem_maxpool_bn_relu_eval_bwd", P(g), P(tape["idx"]), P(tape["carg"]), P(c0), P(st0[0]),
+                 P(st0[1]), P(st0[2]), P(st0[3]), P(store.param(gn + ".weight")),
+                 P(store.grad(gn + ".weight")) if pgrad else None, P(store.grad(gn + ".bias")) if pgrad else None,
+                 P(g_c0), P(store.stat_acc(self.bn1, "bwd", c0.numel() // 64)) if pgrad else None,
+                 N, H1, W1, 64, stream_ptr())
+            yield
+            if pgrad:
+                self._wgrad(tape["x"], g_c0, N, tape["H"], tape["W"], self.stem, store)
+            self._stem_dx(tape, g_c0, store)
+            return
         ws = store.stat_acc(self.bn1, "bwd", c0.numel() // 64)
         call("avt_stem_maxpool_bn_relu_bwd", P(g), P(tape["idx"]), P(tape["carg"]), P(c0), P(st0[0]), P(st0[1]),
              P(st0[2]), P(st0[3]), P(store.param(self.bn1.prefix + ".weight")),
@@ -532,6 +585,10 @@ class Trunk:
              N, H1, W1, 64, stream_ptr())
         yield
         self._wgrad(tape["x"], g_c0, N, tape["H"], tape["W"], self.stem, store)
+        self._stem_dx(tape, g_c0, store)
+
+    def _stem_dx(self, tape: Dict, g_c0: torch.Tensor, store: Store):
+        N = tape["N"]
         if tape.get("want_dx"):  # d(loss)/d(input), NCHW fp32 (a standalone trunk whose input requires grad)
             gx = torch.empty(N, self.stem.cin, tape["H"], tape["W"], device=g_c0.device, dtype=torch.float32)
             call("avt_conv_stem_dgrad", P(g_c0), P(store.param(self.stem.name)), P(gx), N, tape["H"], tape["W"],

@@ -19,6 +19,9 @@
  *   avt_bn_apply_mask,           BasicBlock output relu(bn2(c2) + residual) (base_models.py:64-67) with its ReLU
  *   avt_bn_bwd_mask,             mask kept as bits; the backward of bn2 (+ downsample.1) from those bits, and the
  *   avt_conv2d_dgrad_mask        identity block's input gradient dgrad(conv1) + g * mask without a stored g'
+ *   avt_bn_eval_bwd,             the same BatchNorm2d layers in eval mode (running statistics, nn.Module.eval() at
+ *   avt_bn_eval_bwd_mask,        test.py:85): the backward of the per-channel affine map, with the mask from y / the
+ *   avt_stem_*_eval_bwd          pre-activation, from the avt_bn_apply_mask bits, and through the stem's max-pool
  *   (avt_set_*: A/B knobs between measured kernel variants, in avt_tuning.h -- not part of this boundary)
  *   avt_audio_pool_norm_fwd/bwd  nn.AdaptiveMaxPool2d((1,1)) + F.normalize(dim=1) (model.py:96, 120-122)
  *   avt_hardway_fwd/bwd          AVENet.forward head: normalize, A/A0 einsums, sigmoid trimap,
@@ -294,6 +297,13 @@ int avt_bn_bwd_mask(const void* g, const void* mask, const avt_bn_bwd_target* t1
  * dgamma == dbeta == NULL needs no workspace and is purely elementwise. */
 int avt_bn_eval_bwd(const void* g, const void* y, const float* mscale, const float* mshift, const avt_bn_bwd_target* t1,
                     const avt_bn_bwd_target* t2, void* gmask_out, long long rows, int C, void* stream);
+/* avt_bn_eval_bwd with g' = g * mask bits ([rows][C/8] u8 of avt_bn_apply_mask: bit e of byte j is channel 8j+e) -- the
+ * backward of a 2-D BasicBlock output under running statistics; t2 (optional) shares g' (bn2 + downsample.1: g and the
+ * mask are read once for both).  Rows are dealt and the sums ordered as in avt_bn_eval_bwd: where the bits equal
+ * [out > 0] the results are those of avt_bn_eval_bwd(y = out) bit for bit.  A target with dgamma == dbeta == NULL needs
+ * no workspace and reduces nothing. */
+int avt_bn_eval_bwd_mask(const void* g, const void* mask, const avt_bn_bwd_target* t1, const avt_bn_bwd_target* t2,
+                         long long rows, int C, void* stream);
 /* avt_bn_bwd for a g' that is already masked and whose reductions a dgrad epilogue already added
  * into the workspace (avt_conv2d_dgrad_bn): finalize + apply only */
 int avt_bn_bwd_premasked(const void* gm, const void* xc, const float* mean, const float* invstd, const float* gamma,
@@ -312,6 +322,16 @@ int avt_stem_maxpool_bn_relu_bwd(const void* gy, const void* idx, const void* ca
                                  const float* shift, const float* mean, const float* invstd, const float* gamma,
                                  float* dgamma, float* dbeta, void* gc, void* workspace, int N, int H, int W, int C,
                                  void* stream);
+/* the stem backward under running statistics (mean = running_mean, invstd = rsqrt(running_var + eps)), one pass from
+ * the pooled gradient gy [N,P,Q,C] to gc [N,H,W,C]: gc = gamma*invstd * [fma(c, scale, shift) > 0] * (sum of gy over the
+ * windows whose idx selects the pixel) -- no mean terms; a pixel no window selects gets +0.  dgamma / dbeta (optional,
+ * accumulated): sum g'*(carg - mean)*invstd / sum g' over the pooled rows, through the fixed-order slot workspace
+ * (avt_bn_bwd_workspace(N*H*W, C), bitwise reproducible); both NULL: carg, mean and workspace are not read.
+ * Shape limits as avt_stem_maxpool_bn_relu_bwd. */
+int avt_stem_maxpool_bn_relu_eval_bwd(const void* gy, const void* idx, const void* carg, const void* c,
+                                      const float* scale, const float* shift, const float* mean, const float* invstd,
+                                      const float* gamma, float* dgamma, float* dbeta, void* gc, void* workspace, int N,
+                                      int H, int W, int C, void* stream);
 
 /* ---- pooling ---- */
 int avt_maxpool3s2_fwd(const void* x, void* y, void* idx, int N, int H, int W, int C, void* stream);
