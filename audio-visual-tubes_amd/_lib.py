@@ -82,6 +82,9 @@ SIGNATURES = {
     "avt_wgrad_reduce_batch": (_I, [ctypes.POINTER(SlabReduceDesc), _I, _P]),
     "avt_bn_acc_doubles": (_Z, [_L, _I]),
     "avt_conv2d_fwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "avt_conv2d_fwd_bias": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P]),
+    "avt_fold_desc_bytes": (_Z, []),
+    "avt_fold_conv_bn_batched": (_I, [_P, _I, _L, _P]),
     "avt_conv2d_dgrad": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "avt_conv2d_dgrad_bn": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, ctypes.POINTER(DgradBnEpi), _P]),
     "avt_bn_bwd_premasked": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _P]),
@@ -253,7 +256,27 @@ def lib() -> ctypes.CDLL:
     return _lib
 
 
+# Entry points that write parameters or BatchNorm running statistics behind torch's back (raw pointers: the
+# tensors' _version counters do not move).  Every call of one advances param_write_gen(), which the folded
+# inference path (engine.AVEngine.fold_state) compares; a replayed HIP graph that holds such a launch must call
+# note_param_write() itself (train.py does).
+PARAM_WRITERS = frozenset({"avt_adam_step", "avt_adam_step_dev", "avt_adam_apply_dev", "avt_bn_finalize",
+                           "avt_bn_finalize_rep"})
+_param_write_gen = 0
+
+
+def note_param_write() -> None:
+    global _param_write_gen
+    _param_write_gen += 1
+
+
+def param_write_gen() -> int:
+    return _param_write_gen
+
+
 def call(name: str, *args) -> int:
+    if name in PARAM_WRITERS:
+        note_param_write()
     rc = getattr(lib(), name)(*args)
     if rc != 0:
         msg = lib().avt_last_error().decode(errors="replace")

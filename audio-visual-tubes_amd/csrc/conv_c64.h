@@ -53,7 +53,8 @@ __device__ __forceinline__ float c64_swap1(float v) {
   return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0xB1, 0xF, 0xF, true));
 }
 
-// ADD: 0 none, 1 dx = dgrad + add, 2 dx = dgrad + add * mask bits.  NWAVE 4: each wave a 64x64 sub-tile
+// ADD: 0 none, 1 dx = dgrad + add, 2 dx = dgrad + add * mask bits, 3 (fwd) the bias epilogue of
+// avt_conv2d_fwd_bias: out = [relu](acc + bias[c] (+ add)), all in fp32 from the accumulators, rounded once.  NWAVE 4: each wave a 64x64 sub-tile
 // (TM = 2); NWAVE 8: 32x64 (TM = 1), two waves per SIMD to cover each other's non-MFMA issue
 template <int MODE, int ADD, int NWAVE = 4>
 __global__ __launch_bounds__(NWAVE * 64, 1) void conv_c64_kernel(GemmNTParams p, C64Args ca) {
@@ -145,6 +146,15 @@ __global__ __launch_bounds__(NWAVE * 64, 1) void conv_c64_kernel(GemmNTParams p,
   // epilogue stores (buffer stores, issued unconditionally -- rows past M get an out-of-range offset --
   // so the count is exact; wave 0's statistics atomics only make its wait stricter); before half 1:
   // nothing.
+  float bcol[2];  // ADD 3: the bias of this lane's column in each 32-column block
+  bool b_res = false, b_relu = false;
+  if constexpr (ADD == 3) {
+    static_assert(MODE == MODE_FWD, "the bias epilogue is a forward epilogue");
+#pragma unroll
+    for (int j = 0; j < 2; ++j) bcol[j] = p.bias[j * 32 + frow];
+    b_res = p.add != nullptr;
+    b_relu = p.relu != 0;
+  }
   int tile = tlo + jb;
   double st_s = 0.0, st_m2 = 0.0, st_r = 0.0;  // BN partials of this block's tiles (threads < 64)
   issue_half(tile, 0);
@@ -281,15 +291,34 @@ __global__ __launch_bounds__(NWAVE * 64, 1) void conv_c64_kernel(GemmNTParams p,
           const int r = wid * WR + i * 32 + (v & 3) + 8 * (v >> 2) + 4 * fhalf + (odd ? 1 : 0);
           okv[u] = r < rows_valid;
           offs[u] = (size_t)(m0 + (okv[u] ? r : 0)) * 64 + c;  // element offset of the pair
-          if (ADD) av[u] = *reinterpret_cast<const unsigned*>(p.add + offs[u]);
-          if (ADD == 2) mv[u] = p.amask[offs[u] >> 3];
+          if constexpr (ADD == 3) {
+            if (b_res) av[u] = *reinterpret_cast<const unsigned*>(p.add + offs[u]);
+          } else {
+            if (ADD) av[u] = *reinterpret_cast<const unsigned*>(p.add + offs[u]);
+            if (ADD == 2) mv[u] = p.amask[offs[u] >> 3];
+          }
         }
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
-          const float a0 = acc[i][j][2 * u], a1 = acc[i][j][2 * u + 1];
+          float a0 = acc[i][j][2 * u], a1 = acc[i][j][2 * u + 1];
+          if constexpr (ADD == 3) {  // (the neighbour lane's values arrive with its own column's bias)
+            a0 += bcol[j];
+            a1 += bcol[j];
+          }
           const float r0 = c64_swap1(a0), r1 = c64_swap1(a1);
           unsigned o = odd ? pack2(r1, a1) : pack2(a0, r0);
-          if (ADD) {
+          if constexpr (ADD == 3) {
+            float lo = odd ? r1 : a0, hi = odd ? a1 : r0;
+            if (b_res) {
+              lo += bf2f(av[u] & 0xffff);
+              hi += bf2f(av[u] >> 16);
+            }
+            if (b_relu) {
+              lo = fmaxf(lo, 0.f);
+              hi = fmaxf(hi, 0.f);
+            }
+            o = pack2(lo, hi);
+          } else if (ADD) {
             unsigned a = av[u];
             if (ADD == 2) {
               const unsigned bits = mv[u] >> (c & 7);

@@ -173,6 +173,40 @@ __device__ __forceinline__ void epi_store_bn(const GemmNTParams& p, const bf16_t
   }
 }
 
+// Store of the BIAS forward instantiations (avt_conv2d_fwd_bias).  Ct already holds bf16(acc + bias): the kernels add
+// the per-channel fp32 bias where the accumulators become the LDS tile, before the first rounding.  Here the
+// residual (p.add, optional, may alias out) is added in fp32 to that bf16 value and rounded once more -- the
+// roundings of avt_bn_apply's residual form -- and the ReLU (p.relu) clears what is negative (to +0).  A function
+// of its own: the plain store below keeps its code.
+template <int NT, int BM, int BN, typename OrowFn>
+__device__ __forceinline__ void epi_store_act(const GemmNTParams& p, const bf16_t* Ct, int ct_ld, int n0,
+                                              int rows_valid, OrowFn orow) {
+  constexpr int OCPR = BN / 8;
+  const bool has_add = p.add != nullptr, relu = p.relu != 0;
+  for (int idx = threadIdx.x; idx < BM * OCPR; idx += NT) {
+    const int r = idx / OCPR, cc = idx - r * OCPR;
+    if (r >= rows_valid) continue;
+    u32x4 v = *reinterpret_cast<const u32x4*>(Ct + r * ct_ld + cc * 8);
+    const size_t off = orow(r) * (size_t)p.Ng + n0 + cc * 8;
+    unsigned* vv = reinterpret_cast<unsigned*>(&v);
+    if (has_add) {
+      const u32x4 a = *reinterpret_cast<const u32x4*>(p.add + off);
+      const unsigned* aa = reinterpret_cast<const unsigned*>(&a);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float lo = bf2f(vv[e] & 0xffff) + bf2f(aa[e] & 0xffff);
+        const float hi = bf2f(vv[e] >> 16) + bf2f(aa[e] >> 16);
+        vv[e] = pack2(lo, hi);
+      }
+    }
+    if (relu) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) vv[e] &= (vv[e] & 0x8000u ? 0u : 0x0000ffffu) | (vv[e] & 0x80000000u ? 0u : 0xffff0000u);
+    }
+    *reinterpret_cast<u32x4*>(p.out + off) = v;
+  }
+}
+
 // EPI = false: the plain store (+ add) -- the forward and plain-dgrad instantiations keep the register
 // footprint of their main loop (the BN epilogue's load groups would raise it and cost occupancy).
 template <int NT, int BM, int BN, bool EPI, typename OrowFn, int UMAX = 4>

@@ -667,7 +667,7 @@ extern "C" int avt_set_wgrad_slots_pct(int pct) {
 // ------------------------------------------------------------------------------------------------
 static inline int conv_out(int in, int k, int st, int pad) { return (in + 2 * pad - k) / st + 1; }
 
-template <int MODE, int WM, int WN, int TM, int TN, int NST, int BK>
+template <int MODE, int WM, int WN, int TM, int TN, int NST, int BK, bool BIAS = false>
 static void launch_pipe_one(const GemmNTParams& p, const NTPipeArgsV& ta0, hipStream_t st) {
   constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
   const int grid = ((p.M + BM - 1) / BM) * (p.Ng / BN);
@@ -681,7 +681,10 @@ static void launch_pipe_one(const GemmNTParams& p, const NTPipeArgsV& ta0, hipSt
     ta.cdiv_hw[k] = make_magic((unsigned)(oh > 0 && ow > 0 ? oh * ow : 1));
     ta.cdiv_ow[k] = make_magic((unsigned)(ow > 0 ? ow : 1));
   }
-  if (p.IT > 1 || p.OT > 1 || p.KT > 1 || ta.ntaps > 32) {  // Conv3d / the folded 49-tap video stem
+  if constexpr (BIAS) {  // avt_conv2d_fwd_bias: a 2-D forward of at most 9 taps
+    hipLaunchKernelGGL((conv_nt_pipe_kernel<MODE, WM, WN, TM, TN, NST, BK, false, false, true>), dim3(grid),
+                       dim3(WM * WN * 64), 0, st, p, narrow_args(ta));
+  } else if (p.IT > 1 || p.OT > 1 || p.KT > 1 || ta.ntaps > 32) {  // Conv3d / the folded 49-tap video stem
     if constexpr (MODE == MODE_FWD)
       hipLaunchKernelGGL((conv_nt_pipe_kernel<MODE, WM, WN, TM, TN, NST, BK, true>), dim3(grid), dim3(WM * WN * 64), 0,
                          st, p, ta);
@@ -811,6 +814,30 @@ static void launch_glds(const GemmNTParams& p, hipStream_t st) {
       }
 }
 
+// launch_glds's forward branch for the bias-epilogue instantiations (avt_conv2d_fwd_bias): all R*S taps, one launch
+template <int WM, int WN, int TM, int TN, int NST, int BK = 32>
+static void launch_glds_bias(const GemmNTParams& p, hipStream_t st) {
+  if constexpr (BK == 64) {
+    if (p.IC % 64 != 0) {  // a 64-deep k-tile needs whole 64-channel taps
+      launch_glds_bias<2, 2, 2, (WN * TN * 32) / 64, 3, 32>(p, st);
+      return;
+    }
+  }
+  NTPipeArgsV ta{};
+  const int batch = p.M / (p.OH * p.OW);
+  ta.act_bytes = (unsigned)((size_t)batch * p.IH * p.IW * p.IC * 2);
+  ta.w_bytes = (unsigned)((size_t)p.Ng * p.Kg * 2);
+  ta.ntaps = p.R * p.S;
+  for (int r = 0; r < p.R; ++r)
+    for (int s = 0; s < p.S; ++s) {
+      const int t = r * p.S + s;
+      ta.tap_w[t] = t;
+      ta.tap_dy[t] = r - p.pad;
+      ta.tap_dx[t] = s - p.pad;
+    }
+  launch_pipe_one<MODE_FWD, WM, WN, TM, TN, NST, BK, true>(p, ta, st);
+}
+
 constexpr int kHaloPR = 416;  // patch rows the halo kernels' LDS holds: 256 + 2W + 2 <= 416 -> W <= 79
 
 // 3x3 / stride 1 / pad 1 Conv2d, 64-channel multiples, image width <= 79: the halo-reuse kernel
@@ -848,14 +875,15 @@ static bool use_small_tile(const GemmNTParams& p, int BN) {
   return blocks128 * 100 < (long long)g_small_tile_pct * num_cus();
 }
 
-template <int MODE, int WM, int WN, int TM, int TN, int NSTB, int PRMAX, bool EPI, int OPT = 0>
+template <int MODE, int WM, int WN, int TM, int TN, int NSTB, int PRMAX, bool EPI, int OPT = 0, bool BIAS = false>
 static void launch_halo_one(const GemmNTParams& p, const HaloArgs& ha, int grid, hipStream_t st) {
-  hipLaunchKernelGGL((conv_halo_kernel<MODE, WM, WN, TM, TN, NSTB, PRMAX, EPI, false, 0, OPT>), dim3(grid),
+  hipLaunchKernelGGL((conv_halo_kernel<MODE, WM, WN, TM, TN, NSTB, PRMAX, EPI, false, 0, OPT, BIAS>), dim3(grid),
                      dim3(WM * WN * 64), 0, st, p, ha);
 }
 
 // OPT 4: the Conv3d 3x3x3 / stride 1 / pad 1 form (conv_halo.h; forward only)
-template <int MODE, int WM, int WN, int TM, int TN, int NSTB = 3, int PRMAX = kHaloPR, int OPT = 0>
+// BIAS: the bias-epilogue instantiation (avt_conv2d_fwd_bias; forward, no split-K)
+template <int MODE, int WM, int WN, int TM, int TN, int NSTB = 3, int PRMAX = kHaloPR, int OPT = 0, bool BIAS = false>
 static void launch_halo(const GemmNTParams& p, hipStream_t st, int ksplit = 1, float* part = nullptr,
                         int* cnt = nullptr) {
   constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
@@ -888,13 +916,17 @@ static void launch_halo(const GemmNTParams& p, hipStream_t st, int ksplit = 1, f
     ha.div_t = make_magic((unsigned)p.IT);
   }
   const int grid = ((p.M + BM - 1) / BM) * (p.Ng / BN) * ksplit;
-  if (grid > 0 && ksplit > 1) {
-    hipLaunchKernelGGL((conv_halo_kernel<MODE, WM, WN, TM, TN, NSTB, PRMAX, false, true>), dim3(grid),
-                       dim3(WM * WN * 64), 0, st, p, ha);
-    return;
+  if constexpr (!BIAS) {
+    if (grid > 0 && ksplit > 1) {
+      hipLaunchKernelGGL((conv_halo_kernel<MODE, WM, WN, TM, TN, NSTB, PRMAX, false, true>), dim3(grid),
+                         dim3(WM * WN * 64), 0, st, p, ha);
+      return;
+    }
   }
   if (grid <= 0) return;
-  if constexpr ((OPT & 4) != 0)
+  if constexpr (BIAS)
+    launch_halo_one<MODE, WM, WN, TM, TN, NSTB, PRMAX, false, OPT, true>(p, ha, grid, st);
+  else if constexpr ((OPT & 4) != 0)
     launch_halo_one<MODE, WM, WN, TM, TN, NSTB, PRMAX, false, OPT>(p, ha, grid, st);
   else if (MODE == MODE_DGRAD && p.bx != nullptr)
     launch_halo_one<MODE, WM, WN, TM, TN, NSTB, PRMAX, true, OPT>(p, ha, grid, st);
@@ -1006,7 +1038,8 @@ static bool c64_eligible(const GemmNTParams& p) {
          p.IW == p.OW && 256 + 2 * p.OW + 2 <= c64::PRMAX && p.bx == nullptr && (p.add == nullptr || p.add != p.out);
 }
 
-template <int MODE>
+// BIAS: the bias-epilogue instantiation (avt_conv2d_fwd_bias; conv_c64_kernel's ADD 3, on the default 8-wave form)
+template <int MODE, bool BIAS = false>
 static void launch_c64(const GemmNTParams& p, hipStream_t st) {
   C64Args ca{};
   const int batch = p.M / (p.OH * p.OW);
@@ -1037,6 +1070,10 @@ static void launch_c64(const GemmNTParams& p, hipStream_t st) {
   const int rounds = (ca.tiles + cus - 1) / cus;
   const int grid = rounds > 0 ? (ca.tiles + rounds - 1) / rounds : 0;
   if (grid <= 0) return;
+  if constexpr (BIAS) {
+    hipLaunchKernelGGL((conv_c64_kernel<MODE_FWD, 3, 8>), dim3(grid), dim3(512), 0, st, p, ca);
+    return;
+  }
   // 8-wave blocks (two waves per SIMD; default): layer-1 fwd/dgrad 519/630 -> 638/762 TFLOP/s (vision), step
   // 12.61 k -> 12.86 k clips/s in the same-box A/B; AVT_C64_WAVES=4: the 4-wave form
   static const int w8 = !(getenv("AVT_C64_WAVES") && atoi(getenv("AVT_C64_WAVES")) == 4);
@@ -1283,6 +1320,85 @@ static int conv2d_fwd_impl(const void* x, const void* wpack, void* y, double* bn
     launch_nt<MODE_FWD, 8, 128, 64>(p, st);
   }
   return check_launch("conv2d_fwd");
+}
+
+// The planner of avt_conv2d_fwd_bias: launch_nt's choice of kernel family and tile for the shape under the same
+// planner knobs (c64 / halo 64-row, 4-wave, 8-wave / tap gather and its tiles by GEMM size), so a shape runs the
+// bias epilogue on the main loop its plain forward runs.  The knobs that only trade ring depth or wave layout
+// (halo stages, halo8 form / nst / tps2, AVT_C64_WAVES, the nt64 / nt128 tile overrides) stay at their defaults here:
+// they do not change a result bit, and each would cost another instantiation.  No split-K.
+static void launch_nt_bias(const GemmNTParams& p, hipStream_t st) {
+  if (c64_eligible(p)) {
+    launch_c64<MODE_FWD, true>(p, st);
+    return;
+  }
+  if (g_nt128_config < 0 && (g_nt64_config < 0 || g_nt64_config == 1) &&
+      use_small_tile(p, p.Ng % 128 == 0 ? 128 : 64)) {
+    if (p.Ng % 128 != 0)
+      launch_glds_bias<2, 2, 1, 1, 3>(p, st);  // 64 x 64, k32, 3 stages
+    else if (halo_eligible(p) && 64 + 2 * p.OW + 2 <= 104)
+      launch_halo<MODE_FWD, 2, 2, 1, 2, 3, 104, 0, true>(p, st);  // 64 x 128 halo tile
+    else
+      launch_glds_bias<2, 2, 1, 2, 3>(p, st);  // 64 x 128, k32, 3 stages
+    return;
+  }
+  if (halo_eligible(p)) {
+    if (p.Ng % 128 == 0 && (g_halo == 2 || 128 + 2 * p.OW + 2 > 168 || halo8_pick(p))) {
+      if (256 + 2 * p.OW + 2 <= 336)
+        launch_halo<MODE_FWD, 4, 2, 2, 2, 3, 336, 0, true>(p, st);  // 256 x 128, 8 waves, W <= 39
+      else
+        launch_halo<MODE_FWD, 4, 2, 2, 2, 2, kHaloPR, 0, true>(p, st);  // W <= 79
+    } else if (g_halo == 2) {
+      launch_halo<MODE_FWD, 4, 2, 2, 1, 3, kHaloPR, 0, true>(p, st);  // 256 x 64, 8 waves (A/B only)
+    } else {
+      launch_halo<MODE_FWD, 2, 2, 2, 2, 2, 168, 0, true>(p, st);  // 128 x 128, 4 waves
+    }
+    return;
+  }
+  if (p.Ng % 128 == 0) {
+    if (p.M >= 65536)
+      launch_glds_bias<4, 2, 2, 2, 3>(p, st);  // 256 x 128, 8 waves, k32, 3 stages
+    else
+      launch_glds_bias<2, 2, 2, 2, 2, 64>(p, st);  // 128 x 128, k64, 2 stages
+  } else {
+    launch_glds_bias<2, 2, 2, 1, 3>(p, st);  // 128 x 64, 3 stages
+  }
+}
+
+// Forward conv with BatchNorm folded in (include/avt.h): y = [relu](conv(x, wpack) + bias[k] (+ residual)).
+extern "C" int avt_conv2d_fwd_bias(const void* x, const void* wpack, void* y, int N, int H, int W, int Cp, int K,
+                                   int R, int S, int stride, int pad, int Kg, const float* bias, const void* residual,
+                                   int relu, void* stream) {
+  AVT_REQUIRE(x && wpack && y, "conv2d_fwd_bias: null pointer");
+  AVT_REQUIRE(bias, "conv2d_fwd_bias: bias is required (avt_conv2d_fwd is the conv without one)");
+  AVT_REQUIRE(residual == nullptr || residual != y, "conv2d_fwd_bias: residual must not alias y");
+  AVT_REQUIRE(N >= 1 && H >= 1 && W >= 1, "conv2d_fwd_bias: empty input");
+  AVT_REQUIRE(K >= 64 && K % 64 == 0, "conv2d_fwd_bias: K=%d must be a multiple of 64", K);
+  AVT_REQUIRE(Cp >= 32 && Cp % 32 == 0, "conv2d_fwd_bias: C=%d must be a multiple of 32 (the stems keep avt_conv2d_fwd)", Cp);
+  AVT_REQUIRE(R >= 1 && S >= 1 && R * S <= 9, "conv2d_fwd_bias: at most 9 taps");
+  AVT_REQUIRE(Kg == R * S * Cp, "conv2d_fwd_bias: Kg=%d must equal R*S*C", Kg);
+  AVT_REQUIRE(stride == 1 || stride == 2, "conv2d_fwd_bias: stride must be 1 or 2");
+  AVT_REQUIRE(pad >= 0 && H + 2 * pad >= R && W + 2 * pad >= S, "conv2d_fwd_bias: empty output");
+  AVT_REQUIRE(conv_variant() == 1, "conv2d_fwd_bias: needs the LDS-DMA conv kernels (AVT_CONV_VARIANT=1)");
+  GemmNTParams p{};
+  p.act = (const bf16_t*)x;
+  p.wmat = (const bf16_t*)wpack;
+  p.out = (bf16_t*)y;
+  p.add = (const bf16_t*)residual;
+  p.bias = bias;
+  p.relu = relu ? 1 : 0;
+  p.IH = H; p.IW = W; p.IC = Cp;
+  p.OH = conv_out(H, R, stride, pad);
+  p.OW = conv_out(W, S, stride, pad);
+  p.IT = p.OT = p.KT = 1;
+  p.M = N * p.OH * p.OW;
+  AVT_REQUIRE((size_t)N * H * W * Cp * 2 < (1ull << 31) && (size_t)p.M * K * 2 < (1ull << 31),
+              "conv2d_fwd_bias: activation tensors must stay below 2 GiB (32-bit buffer offsets)");
+  p.Ng = K;
+  p.Kg = Kg;
+  p.R = R; p.S = S; p.stride = stride; p.pad = pad;
+  launch_nt_bias(p, (hipStream_t)stream);
+  return check_launch("conv2d_fwd_bias");
 }
 
 static int conv2d_dgrad_impl(const void* dy, const void* wt, void* dx, const void* add, const void* add_mask, int N,

@@ -71,8 +71,10 @@ constexpr int halo_blocks_per_cu() {
 // in frame f reads frame f + dt of its own clip wherever the spatial tap is valid, except across the clip ends: a
 // patch row is zeroed at the DMA (kOOB) when dt = +1 and its pixel is a clip's frame 0, or dt = -1 and frame T - 1 --
 // rows only an output frame -1 or T would read.  The per-lane spatial tap masks are the 2-D ones.
+// BIAS: a forward with the bias epilogue (avt_conv2d_fwd_bias), as conv_nt_pipe_kernel's: bias before the first rounding
+// (at the LDS tile), residual and ReLU in the store.  The flag is independent of OPT: the Conv3d form may take it too.
 template <int MODE, int WM, int WN, int TM, int TN, int NSTB, int PRMAX, bool EPI = false, bool SPLIT = false,
-          int PREF = 0, int OPT = 0>
+          int PREF = 0, int OPT = 0, bool BIAS = false>
 __global__ __launch_bounds__(WM * WN * 64, (halo_blocks_per_cu<WN, TN, NSTB, PRMAX, (OPT & 2) ? 2 : 1>())) void conv_halo_kernel(
     GemmNTParams p, HaloArgs ha) {
   // fragment geometry: FM x FN MFMA tiles of FR rows per wave, KS k-steps of KD per 64-channel tap
@@ -583,15 +585,31 @@ __global__ __launch_bounds__(WM * WN * 64, (halo_blocks_per_cu<WN, TN, NSTB, PRM
     }
   }
   bf16_t* Ct = reinterpret_cast<bf16_t*>(smem);
+  float bcol[FN];  // BIAS: the bias of this lane's column of each column block
+  if constexpr (BIAS) {
+    static_assert(MODE == MODE_FWD && !EPI && !SPLIT, "the bias epilogue: forward, no split-K");
+#pragma unroll
+    for (int j = 0; j < FN; ++j) bcol[j] = p.bias[n0 + wn * (BN / WN) + j * FR + frow];
+  }
 #pragma unroll
   for (int i = 0; i < FM; ++i)
 #pragma unroll
     for (int j = 0; j < FN; ++j)
 #pragma unroll
-      for (int v = 0; v < AV; ++v) Ct[acc_row(i, v) * CT_LD + wn * (BN / WN) + j * FR + frow] = f2bf(acc[i][j][v]);
+      for (int v = 0; v < AV; ++v) {
+        if constexpr (BIAS)
+          Ct[acc_row(i, v) * CT_LD + wn * (BN / WN) + j * FR + frow] = f2bf(acc[i][j][v] + bcol[j]);
+        else
+          Ct[acc_row(i, v) * CT_LD + wn * (BN / WN) + j * FR + frow] = f2bf(acc[i][j][v]);
+      }
   __syncthreads();
-  if (!HALO_DBG(16))
-    epi_store<NT, BM, BN, EPI>(p, Ct, CT_LD, n0, rows_valid, mt, (p.M + BM - 1) / BM,
-                               [&](int r) -> size_t { return (size_t)(m0 + r); },
-                        reinterpret_cast<float*>(smem));
+  if constexpr (BIAS) {
+    if (!HALO_DBG(16))
+      epi_store_act<NT, BM, BN>(p, Ct, CT_LD, n0, rows_valid, [&](int r) -> size_t { return (size_t)(m0 + r); });
+  } else {
+    if (!HALO_DBG(16))
+      epi_store<NT, BM, BN, EPI>(p, Ct, CT_LD, n0, rows_valid, mt, (p.M + BM - 1) / BM,
+                                 [&](int r) -> size_t { return (size_t)(m0 + r); },
+                                 reinterpret_cast<float*>(smem));
+  }
 }

@@ -151,7 +151,10 @@ __device__ __forceinline__ int swz_rb(int row, int chunk) {
 // R3D-18 video trunk and its 49-tap stem); the Conv2d instances keep the 32-bit mask and 2-D row
 // decode (measured: the general form costs the 2-D convs ~3.5 %).
 // EPI: a dgrad with the BatchNorm-backward store epilogue (conv_epi.h; GemmNTParams::bx set).
-template <int MODE, int WM, int WN, int TM, int TN, int NST, int BK = 32, bool VID = false, bool EPI = false>
+// BIAS: a forward with the bias epilogue (avt_conv2d_fwd_bias): the fp32 bias joins the accumulators where they are
+// rounded into the LDS tile; residual and ReLU in the store (conv_epi.h epi_store_act).
+template <int MODE, int WM, int WN, int TM, int TN, int NST, int BK = 32, bool VID = false, bool EPI = false,
+          bool BIAS = false>
 __global__ __launch_bounds__(WM * WN * 64) void conv_nt_pipe_kernel(
     GemmNTParams p, typename std::conditional<VID, NTPipeArgsV, NTPipeArgs>::type ta) {
   typedef typename std::conditional<VID, unsigned long long, unsigned>::type mask_t;
@@ -407,6 +410,12 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_nt_pipe_kernel(
     }
   }
   bf16_t* Ct = reinterpret_cast<bf16_t*>(smem);
+  float bcol[TN];  // BIAS: the bias of this lane's column of each column block
+  if constexpr (BIAS) {
+    static_assert(MODE == MODE_FWD && !EPI, "the bias epilogue is a forward epilogue");
+#pragma unroll
+    for (int j = 0; j < TN; ++j) bcol[j] = p.bias[n0 + wn * (BN / WN) + j * 32 + frow];
+  }
 #pragma unroll
   for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -415,7 +424,10 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_nt_pipe_kernel(
       for (int v = 0; v < 16; ++v) {
         const int r = wm * (BM / WM) + i * 32 + (v & 3) + 8 * (v >> 2) + 4 * fhalf;
         const int c = wn * (BN / WN) + j * 32 + frow;
-        Ct[r * CT_LD + c] = f2bf(acc[i][j][v]);
+        if constexpr (BIAS)
+          Ct[r * CT_LD + c] = f2bf(acc[i][j][v] + bcol[j]);
+        else
+          Ct[r * CT_LD + c] = f2bf(acc[i][j][v]);
       }
   __syncthreads();
   // class mode: class row -> full output pixel (2h'+ph, 2w'+pw)
@@ -426,6 +438,9 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_nt_pipe_kernel(
     const int oh = rem / p.OW, ow = rem - oh * p.OW;
     return ((size_t)n * ta.OHf + 2 * oh + cph) * ta.OWf + 2 * ow + cpw;
   };
-  epi_store<NT, BM, BN, EPI>(p, Ct, CT_LD, n0, rows_valid, mt, (p.M + BM - 1) / BM, orow,
-                             reinterpret_cast<float*>(smem));
+  if constexpr (BIAS)
+    epi_store_act<NT, BM, BN>(p, Ct, CT_LD, n0, rows_valid, orow);
+  else
+    epi_store<NT, BM, BN, EPI>(p, Ct, CT_LD, n0, rows_valid, mt, (p.M + BM - 1) / BM, orow,
+                               reinterpret_cast<float*>(smem));
 }

@@ -29,13 +29,23 @@ struct GemmNTParams {
   // by the same g' (the downsample BN of a first block: bn2 and downsample.1 share the ReLU).
   const bf16_t* bx;
   const bf16_t* by;
-  const float* bst;    // [4][Ng]: scale, shift, mean, invstd
+  // fwd only -- the bias epilogue of the BIAS instantiations (avt_conv2d_fwd_bias: BatchNorm folded into the weights):
+  // out = [relu](acc + bias[column] (+ add)).  bias / relu share the storage of two dgrad-only fields (a launch has
+  // either epilogue, never both), so the parameter block -- and with it every kernel without the bias epilogue --
+  // is laid out as before.
+  union {
+    const float* bst;   // [4][Ng]: scale, shift, mean, invstd
+    const float* bias;  // [Ng] fp32
+  };
   double* bacc;
   const bf16_t* bx2;
   const float* bst2;
   double* bacc2;
-  int bskip00;         // host side: a stride-2 dgrad's class-(0,0) launch stores plain g (another
+  union {
+    int bskip00;       // host side: a stride-2 dgrad's class-(0,0) launch stores plain g (another
                        // kernel -- the downsample dgrad -- adds to those pixels and applies the epilogue)
+    int relu;          // bias epilogue: clamp the result at 0
+  };
   int bslot_base, bslot_total, bappend;
   const unsigned char* amask;  // optional [M][Ng/8] bits: `add` enters masked, add * bit (an identity
                                // block's residual gradient g * [out > 0], from avt_bn_apply_mask's bits)

@@ -133,6 +133,68 @@ __global__ __launch_bounds__(256) void pack_fwd_batched_kernel(const PackDesc* _
   }
 }
 
+// Inference fold of a frozen BatchNorm into the conv in front of it (avt_fold_conv_bn_batched): with
+// s[k] = gamma[k] * rsqrt(running_var[k] + eps), bn(conv(x, w)) = conv(x, w * s) + (beta - running_mean * s).
+// One record per conv, blockIdx.y = record.  The fwd image is pack_fwd_batched_kernel's (same layout, same zero
+// padding) of w[k, ...] * s[k], the product formed in fp32 and rounded to bf16 once; bias[k] = beta[k] - mean[k] * s[k]
+// (two roundings, no fma contraction: the expression torch evaluates for the unfolded eval forward).  plain != 0 (the
+// 7x7 stems, whose BatchNorm stays in avt_stem_bn_relu_maxpool_fwd): the image is the unscaled pack and bias is
+// that kernel's [2][K] (scale, shift).  Every output element is written by one thread from its own inputs: deterministic.
+struct FoldDesc {
+  const float* w;      // [K][R][S][C] fp32
+  bf16_t* fwd;         // [K][Kg]
+  const float* gamma;  // [K]
+  const float* beta;
+  const float* mean;   // running_mean
+  const float* var;    // running_var
+  float* bias;         // [K], or [2][K] (plain)
+  int K, RS, C, Cp, Kg, plain;
+  float eps;
+  int pad_;
+};
+
+__device__ __forceinline__ float fold_scale(const FoldDesc& d, int k) {
+  return __fmul_rn(d.gamma[k], rsqrtf(d.var[k] + d.eps));
+}
+
+__global__ __launch_bounds__(256) void fold_conv_bn_batched_kernel(const FoldDesc* __restrict__ descs) {
+  const FoldDesc d = descs[blockIdx.y];
+  const int row = d.RS * d.C;
+  const int total = d.K * d.Kg;
+  const int tid = blockIdx.x * 256 + threadIdx.x, nthr = gridDim.x * 256;
+  for (int k = tid; k < d.K; k += nthr) {
+    const float s = fold_scale(d, k);
+    const float b = __fsub_rn(d.beta[k], __fmul_rn(d.mean[k], s));
+    if (d.plain) {
+      d.bias[k] = s;
+      d.bias[d.K + k] = b;
+    } else {
+      d.bias[k] = b;
+    }
+  }
+  if (d.Cp == d.C && d.Kg == row && (d.Kg & 7) == 0 && (((uintptr_t)d.w | (uintptr_t)d.fwd) & 15) == 0) {
+    for (int v = tid; v < total / 8; v += nthr) {
+      const float s = d.plain ? 1.f : fold_scale(d, (v * 8) / d.Kg);  // 8 | Kg: the 8 elements share a row
+      const float4 a = reinterpret_cast<const float4*>(d.w)[2 * v];
+      const float4 b = reinterpret_cast<const float4*>(d.w)[2 * v + 1];
+      u32x4 o;
+      o.x = pack2(__fmul_rn(a.x, s), __fmul_rn(a.y, s));
+      o.y = pack2(__fmul_rn(a.z, s), __fmul_rn(a.w, s));
+      o.z = pack2(__fmul_rn(b.x, s), __fmul_rn(b.y, s));
+      o.w = pack2(__fmul_rn(b.z, s), __fmul_rn(b.w, s));
+      reinterpret_cast<u32x4*>(d.fwd)[v] = o;
+    }
+  } else {
+    for (int t = tid; t < total; t += nthr) {
+      const int k = t / d.Kg, col = t - k * d.Kg;
+      const int rs = col / d.Cp, c = col - rs * d.Cp;
+      float val = 0.f;
+      if (rs < d.RS && c < d.C) val = __fmul_rn(d.w[((size_t)k * d.RS + rs) * d.C + c], d.plain ? 1.f : fold_scale(d, k));
+      d.fwd[t] = f2bf(val);
+    }
+  }
+}
+
 // dgrad image [C][R*S][K] = transpose of w[K][R*S][C] per tap: 64x64 (k, c) tiles through LDS so
 // that both the fp32 reads (along c) and the bf16 writes (along k) are contiguous.  K, C multiples of 64 and 16-byte
 // aligned operands (every conv but the stems): 16-byte loads (4 c) and stores (8 k) per thread; else one element.
@@ -516,6 +578,19 @@ extern "C" int avt_pack_conv_weights_batched(const void* descs, int n, long long
   hipLaunchKernelGGL(pack_dgrad_batched_kernel, dim3((unsigned)tx, n), dim3(256), 0, (hipStream_t)stream,
                      (const PackDesc*)descs);
   return check_launch("pack_conv_weights_batched");
+}
+
+// descs: device array of n FoldDesc records (avt_fold_desc_bytes() each; include/avt.h); one launch folds them all
+extern "C" size_t avt_fold_desc_bytes(void) { return sizeof(FoldDesc); }
+
+extern "C" int avt_fold_conv_bn_batched(const void* descs, int n, long long max_elems, void* stream) {
+  AVT_REQUIRE(descs && n > 0, "fold_conv_bn_batched: bad arguments");
+  AVT_REQUIRE(max_elems >= 0 && max_elems < (1ll << 31), "fold_conv_bn_batched: max_elems out of range");
+  long long bx = (max_elems / 8 + 255) / 256;  // 8 elements per thread
+  bx = bx > 1024 ? 1024 : (bx < 1 ? 1 : bx);
+  hipLaunchKernelGGL(fold_conv_bn_batched_kernel, dim3((unsigned)bx, n), dim3(256), 0, (hipStream_t)stream,
+                     (const FoldDesc*)descs);
+  return check_launch("fold_conv_bn_batched");
 }
 
 // One of the two launches of avt_pack_conv_weights_batched: which = 1 the fwd images, 2 the dgrad images

@@ -16,7 +16,7 @@ from typing import Dict, List, Optional, Tuple
 
 import torch
 
-from ._lib import call, query
+from ._lib import call, param_write_gen, query
 from .trunk import P, Store, Trunk, drive, stream_ptr
 
 
@@ -211,6 +211,12 @@ class _EngineStore(Store):
     def packed(self, spec):
         return self.e.packs[spec.name]
 
+    def folded(self, spec):
+        return self.e.folds[spec.name]
+
+    def folded_stem(self, trunk):
+        return self.e.folds[trunk.stem.name]
+
     def stat_acc(self, bn, kind, rows):
         return self.e.stat_acc(bn, kind, rows)
 
@@ -258,6 +264,10 @@ class AVEngine:
         # the wgrads' split-K slab reduces deferred to one batched launch per trunk and backward segment
         # (avt_wgrad_reduce_batch; AVT_WGRAD_DEFER=1 -- until measured, off: a reduce launch per wgrad, the same bits)
         self.defer_wgrad = os.environ.get("AVT_WGRAD_DEFER", "0") != "0"
+        # folded inference (forward_folded): operands allocated at first use, rebuilt when fold_state() moves
+        self.folds = None
+        self._fold_key = None
+        self.fold_launches = 0  # fold launches so far (one per trunk and rebuild)
 
     def splitk_ws(self, spec, dgrad: bool, N: int, H: int, W: int):
         """(part, cnt) for a split-K conv call (avt_conv2d_splitk_plan), or None: no split for the shape,
@@ -412,6 +422,90 @@ class AVEngine:
         off = first * int(query("avt_pack_desc_bytes"))
         call("avt_pack_conv_weights_part", P(self._pack_table[off:]), n, mx, which, stream_ptr())
 
+    # ----------------------------------------------------------------------------- folded inference
+    BN_EPS = 1e-5  # nn.BatchNorm2d's default, as _bn_finalize (the reference never changes it)
+
+    def _alloc_folds(self):
+        """The folded operands of both trunks (first folded forward): per non-stem conv the bf16 image of
+        w * bn_scale and the fp32 bias, per stem its unscaled image and bn1's [2, 64] (scale, shift); one
+        descriptor table per trunk for avt_fold_conv_bn_batched."""
+        import struct
+
+        dev = self.flat.flat.device
+        self.folds: Dict[str, Tuple[torch.Tensor, torch.Tensor]] = {}
+        self._fold_parts = {}  # trunk prefix -> (descriptor table, records, max elements)
+        for tr in self.trunks2d:
+            pairs = [(tr.stem, tr.bn1)]
+            for b in tr.blocks:
+                pairs += [(b["conv1"], b["bn1"]), (b["conv2"], b["bn2"])]
+                if b["down"] is not None:
+                    pairs.append((b["down"], b["bnd"]))
+            descs, tmax = [], 0
+            for spec, bn in pairs:
+                wf = torch.empty(spec.cout, spec.kg, device=dev, dtype=torch.bfloat16)
+                bias = torch.empty((2, spec.cout) if spec.is_stem else (spec.cout,), device=dev, dtype=torch.float32)
+                self.folds[spec.name] = (wf, bias)
+                ptrs = [self.flat.raw(spec.name), wf, self.flat.raw(bn.prefix + ".weight"),
+                        self.flat.raw(bn.prefix + ".bias"), self.flat.rawbuf(bn.prefix + ".running_mean"),
+                        self.flat.rawbuf(bn.prefix + ".running_var"), bias]
+                descs.append(struct.pack("<QQQQQQQiiiiiifi", *[t.data_ptr() for t in ptrs], spec.cout, spec.k * spec.k,
+                                         spec.cin, spec.cp, spec.kg, int(spec.is_stem), self.BN_EPS, 0))
+                tmax = max(tmax, spec.cout * spec.kg)
+            assert len(descs[0]) == int(query("avt_fold_desc_bytes"))
+            table = torch.frombuffer(bytearray(b"".join(descs)), dtype=torch.uint8).to(dev)
+            self._fold_parts[tr.prefix] = (table, len(descs), tmax)
+
+    def fold_state(self):
+        """What the folded operands depend on.  torch's in-place writes to the flat parameter / buffer storage
+        (optimizer steps, load_state_dict, copy_, mul_ on any view: views share their base's version counter)
+        move the _version counters; libavt's own writes through raw pointers (Adam, the BN finalize of a
+        train-mode forward, a replayed step graph) move _lib.param_write_gen(); a moved or re-created store has
+        other data pointers.  (A write through ``tensor.data`` is invisible to torch itself: call
+        AVENet.invalidate_folded() after one.)"""
+        f = self.flat
+        return (f.flat._version, f.bflat._version, param_write_gen(), f.flat.data_ptr(), f.bflat.data_ptr())
+
+    def fold_trunk(self, tr: Trunk):
+        """One launch: refold this trunk's BatchNorms into its convs from the flat store (current stream)."""
+        table, n, mx = self._fold_parts[tr.prefix]
+        call("avt_fold_conv_bn_batched", P(table), n, mx, stream_ptr())
+        self.fold_launches += 1
+
+    def forward_folded(self, image: torch.Tensor, audio: torch.Tensor, layer_io: bool = False):
+        """forward(training=False) on the folded inference path (AVENet.enable_folded_inference): each trunk as
+        Trunk.forward_folded -- no BatchNorm launch, no per-call arithmetic on BN parameters, no weight pack --
+        the two trunks interleaved on two streams as in forward().  The folded operands are rebuilt (one launch
+        per trunk, at the head of its branch) only when fold_state() has moved since they were built.  Returns
+        forward()'s (out, None)."""
+        self._check_inputs(image, audio)
+        if self.folds is None:
+            self._alloc_folds()
+        state = self.fold_state()
+        refold = state != self._fold_key
+        self._fold_key = state
+        io_a = {} if layer_io else None
+        io_v = {} if layer_io else None
+        B, dev = image.shape[0], image.device
+
+        def audio_branch():
+            if refold:
+                self.fold_trunk(self.aud)
+            xa = self._to_nhwc(audio, 1)
+            a = yield from self.aud.forward_folded_iter(xa, self.store, io_a)
+            return (a,) + self._audio_pool(a, B)
+
+        def vision_branch():
+            if refold:
+                self.fold_trunk(self.img)
+            xi = self._to_nhwc(image, 4)
+            return (yield from self.img.forward_folded_iter(xi, self.store, io_v))
+
+        (a, an, amax, anorm), v = self._interleave(audio_branch(), vision_branch(), "FWD")
+        out, _ = self._head_forward(v, an, B)
+        if layer_io:
+            out.update(v_in=io_v["layer4_in"], a=a, a_in=io_a["layer4_in"])
+        return out, None
+
     # ----------------------------------------------------------------------------- forward
     @staticmethod
     def _to_nhwc(x: torch.Tensor, cp: int) -> torch.Tensor:
@@ -421,6 +515,46 @@ class AVEngine:
         call("avt_nchw_to_nhwc_bf16", P(x), P(y), N, C, H, W, cp, stream_ptr())
         return y
 
+    @staticmethod
+    def _check_inputs(image: torch.Tensor, audio: torch.Tensor):
+        if not image.is_cuda or not audio.is_cuda:
+            raise RuntimeError("avt: inputs must be on the GPU (no CPU path)")
+        if image.shape[1] != 3 or audio.shape[1] != 1:
+            raise ValueError(f"avt: expected image [B,3,H,W] and audio [B,1,F,T], got {tuple(image.shape)} "
+                             f"and {tuple(audio.shape)}")
+        if audio.shape[0] != image.shape[0]:
+            raise ValueError("avt: image and audio batch sizes differ")
+
+    @staticmethod
+    def _audio_pool(a: torch.Tensor, B: int):
+        """Audio layer4 map -> (an [B,C] unit vectors, amax, anorm) on the current stream."""
+        C = a.shape[-1]
+        an = torch.empty(B, C, device=a.device, dtype=torch.float32)
+        amax = torch.empty(B, C, device=a.device, dtype=torch.int32)
+        anorm = torch.empty(B, device=a.device, dtype=torch.float32)
+        call("avt_audio_pool_norm_fwd", P(a), P(an), P(amax), P(anorm), B, a.shape[1] * a.shape[2], C, stream_ptr())
+        return an, amax, anorm
+
+    def _head_forward(self, v: torch.Tensor, an: torch.Tensor, B: int):
+        """The hard-way head on (v, an): (the outputs, the tensors a tape keeps for head_backward)."""
+        _, h, w, C = v.shape
+        Pn = h * w
+        L = B + (2 if self.neg else 1)
+        f32 = dict(device=v.device, dtype=torch.float32)
+        inv = torch.empty(B, Pn, **f32)
+        vsum = torch.empty(B, Pn, **f32)
+        A0 = torch.empty(B, Pn, B, **f32)
+        save = torch.empty(int(query("avt_hardway_save_floats", B)), **f32)
+        logits = torch.empty(B, L, **f32)
+        A = torch.empty(B, 1, h, w, **f32)
+        Pos = torch.empty(B, 1, h, w, **f32)
+        Neg = torch.empty(B, 1, h, w, **f32)
+        wA = torch.empty(B, h, w, **f32)
+        call("avt_hardway_fwd", P(v), P(an), B, Pn, C, self.epsilon, self.epsilon2, self.tau, int(self.tri_map),
+             int(self.neg), P(inv), P(vsum), P(A0), P(save), P(logits), P(A), P(Pos), P(Neg), P(wA), stream_ptr())
+        out = {"A": A, "logits": logits, "weighted_A": wA, "Pos": Pos, "Neg": Neg, "v": v}
+        return out, {"inv": inv, "vsum": vsum, "A0": A0, "save": save, "B": B, "P": Pn, "C": C}
+
     def forward(self, image: torch.Tensor, audio: torch.Tensor, training: bool, with_ce: bool = False,
                 ce_scale: float = 1.0, layer_io: bool = False, vision_pre=None, tape: bool = False):
         """tape (with training=False): keep the tape of the eval forward for the running-statistics backward
@@ -428,14 +562,8 @@ class AVEngine:
         for forward hooks registered on imgnet.layer4 / audnet.layer4 (test.py:63).  vision_pre():
         launches issued at the head of the vision trunk's branch (ordered before the head, concurrent
         with the audio trunk)."""
-        if not image.is_cuda or not audio.is_cuda:
-            raise RuntimeError("avt: inputs must be on the GPU (no CPU path)")
-        if image.shape[1] != 3 or audio.shape[1] != 1:
-            raise ValueError(f"avt: expected image [B,3,H,W] and audio [B,1,F,T], got {tuple(image.shape)} "
-                             f"and {tuple(audio.shape)}")
+        self._check_inputs(image, audio)
         B = image.shape[0]
-        if audio.shape[0] != B:
-            raise ValueError("avt: image and audio batch sizes differ")
         # split packing (concurrent trunks): each trunk's fwd operands at the head of its own branch, the
         # dgrad operands (backward only) behind the vision forward, which finishes before the audio one
         split_pack = self.concurrent and self.split_pack
@@ -455,13 +583,7 @@ class AVEngine:
                 self.pack_trunk(self.aud, 1)
             xa = self._to_nhwc(audio, 1)
             a, tape_a = yield from self.aud.forward_iter(xa, self.store, training, io_a, tape)
-            C = a.shape[-1]
-            an = torch.empty(B, C, device=dev, dtype=torch.float32)
-            amax = torch.empty(B, C, device=dev, dtype=torch.int32)
-            anorm = torch.empty(B, device=dev, dtype=torch.float32)
-            call("avt_audio_pool_norm_fwd", P(a), P(an), P(amax), P(anorm), B, a.shape[1] * a.shape[2], C,
-                 stream_ptr())
-            return a, tape_a, an, amax, anorm
+            return (a, tape_a) + self._audio_pool(a, B)
 
         def vision_branch():
             if training:
@@ -479,28 +601,15 @@ class AVEngine:
 
         # audio trunk (side stream) || vision trunk (current stream), launches interleaved
         (a, tape_a, an, amax, anorm), (v, tape_i) = self._interleave(audio_branch(), vision_branch(), "FWD")
-        _, h, w, C = v.shape
-        Pn = h * w
-        L = B + (2 if self.neg else 1)
+        out, saved = self._head_forward(v, an, B)
+        logits = out["logits"]
+        L = logits.shape[1]
         f32 = dict(device=dev, dtype=torch.float32)
-        inv = torch.empty(B, Pn, **f32)
-        vsum = torch.empty(B, Pn, **f32)
-        A0 = torch.empty(B, Pn, B, **f32)
-        save = torch.empty(int(query("avt_hardway_save_floats", B)), **f32)
-        logits = torch.empty(B, L, **f32)
-        A = torch.empty(B, 1, h, w, **f32)
-        Pos = torch.empty(B, 1, h, w, **f32)
-        Neg = torch.empty(B, 1, h, w, **f32)
-        wA = torch.empty(B, h, w, **f32)
-        call("avt_hardway_fwd", P(v), P(an), B, Pn, C, self.epsilon, self.epsilon2, self.tau, int(self.tri_map),
-             int(self.neg), P(inv), P(vsum), P(A0), P(save), P(logits), P(A), P(Pos), P(Neg), P(wA), stream_ptr())
-        out = {"A": A, "logits": logits, "weighted_A": wA, "Pos": Pos, "Neg": Neg, "v": v}
         if layer_io:
             out.update(v_in=io_v["layer4_in"], a=a, a_in=io_a["layer4_in"])
         tape = None
         if keep:
-            tape = {"img": tape_i, "aud": tape_a, "v": v, "a": a, "an": an, "amax": amax, "anorm": anorm,
-                    "inv": inv, "vsum": vsum, "A0": A0, "save": save, "B": B, "P": Pn, "C": C}
+            tape = {"img": tape_i, "aud": tape_a, "v": v, "a": a, "an": an, "amax": amax, "anorm": anorm, **saved}
         if with_ce:
             loss = torch.empty((), **f32)
             dlogits = torch.empty(B, L, **f32) if training else None

@@ -127,7 +127,8 @@ def gt_map_vggss(bboxs, size: int = GT_SIZE) -> np.ndarray:
 def evaluate_hardway(model, batches, gt_maps) -> Tuple[float, float]:
     """The test_hardway loop (train_hardway_1frame.py:187-216): eval-mode forward of each (image,
     spec) batch, localisation of every heatmap against its gt map.  ``batches`` yields (image, spec)
-    GPU tensors; ``gt_maps`` yields the matching [B,224,224] maps.  Returns (cIoU@0.5, AUC)."""
+    GPU tensors; ``gt_maps`` yields the matching [B,224,224] maps.  Returns (cIoU@0.5, AUC).  The forwards run
+    on whatever path the model has enabled: the folded one after ``model.enable_folded_inference()``."""
     was_training = model.training
     model.eval()
     ev = Evaluator()

@@ -313,8 +313,30 @@ class AVENet(nn.Module):
         # shallow copy of this __dict__) create and find them in the model's cache.
         self._engines = {}
         self._avt_eval_backward = False  # enable_eval_backward(): eval-mode (running-statistics BN) backward
+        self._avt_folded = False  # enable_folded_inference(): BatchNorm folded into the convs for no-grad eval calls
         for prefix, net in (("imgnet.", self.imgnet), ("audnet.", self.audnet)):
             net._adopt(self, prefix)
+
+    def enable_folded_inference(self):
+        """Opt in to the folded inference forward: in eval mode, for a call that needs no gradient (under
+        ``torch.no_grad()``, or with nothing requiring grad), each trunk runs with its BatchNorms folded into the
+        conv weights -- 20 conv launches with bias / residual / ReLU epilogues and the fused stem kernel, no
+        BatchNorm pass, no per-call weight pack (engine.AVEngine.forward_folded).  The folded weights are rebuilt,
+        one launch per trunk, whenever a parameter or BN buffer has changed since the last fold (optimizer steps,
+        ``load_state_dict``, ``.to()``, a train-mode forward, in-place edits of a buffer); the outputs agree with
+        the unfolded eval forward to bf16 rounding (weights are rounded after scaling).  Train mode and eval calls
+        that take the autograd path (``enable_eval_backward()``) run exactly as before, as does a model that never
+        calls this.  nn.DataParallel replicas on other GPUs take the unfolded path (their mirror store is refilled
+        on every forward, so a fold would be rebuilt every call).  Idempotent; returns self."""
+        self._avt_folded = True
+        return self
+
+    def invalidate_folded(self):
+        """Force the next folded forward to refold.  Only needed after a write torch cannot see: through
+        ``tensor.data``, or by foreign code holding a raw pointer into the parameters."""
+        for e in self._engines.values():
+            e._fold_key = None
+        return self
 
     def enable_eval_backward(self):
         """Opt in to gradients through the model in eval mode (``model.eval()``: test.py:85, visualize.py:121):
@@ -408,7 +430,10 @@ class AVENet(nn.Module):
         if need_grad:
             A, logits, wA, Pos, Neg = _AVENetFunction.apply(eng, self.training, sink, image, audio, *train_params)
         else:
-            out, _ = eng.forward(image, audio, self.training, layer_io=sink is not None)
+            if not self.training and getattr(self, "_avt_folded", False) and eng.flat is self._flat:
+                out, _ = eng.forward_folded(image, audio, layer_io=sink is not None)
+            else:
+                out, _ = eng.forward(image, audio, self.training, layer_io=sink is not None)
             A, logits, wA, Pos, Neg = out["A"], out["logits"], out["weighted_A"], out["Pos"], out["Neg"]
             if sink is not None:
                 sink.update(out)

@@ -27,6 +27,7 @@ from typing import Optional
 import torch
 import torch.distributed as dist
 
+from ._lib import note_param_write
 from .engine import AVEngine
 from .optim import FlatAdam
 
@@ -282,6 +283,7 @@ class HardWayTrainStep:
         for s, x in zip(self._static_in, inputs):
             if x is not s:
                 s.copy_(x)
+        note_param_write()  # the replayed launches update weights and running statistics (folded inference: _lib.py)
         if self._seg_graphs is not None:
             sync_buffers(self.flat.bflat, self.pg)
             pending: list = []

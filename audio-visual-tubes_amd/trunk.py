@@ -136,6 +136,14 @@ class Store:
     def buffer(self, name: str) -> torch.Tensor: ...
     def grad(self, name: str) -> Optional[torch.Tensor]: ...
     def packed(self, spec: ConvSpec): ...
+    def folded(self, spec: ConvSpec):
+        """(bf16 fwd image of w * bn_scale, fp32 bias [K]) of a non-stem conv with its BatchNorm folded in."""
+        ...
+
+    def folded_stem(self, trunk: "Trunk"):
+        """(the stem's unscaled bf16 fwd image, fp32 [2, 64] (scale, shift) of bn1 under running statistics)."""
+        ...
+
     def stat_acc(self, bn: "BNSpec", kind: str, rows: int) -> torch.Tensor:
         """fp64 statistics accumulator of a BN over `rows` rows ('fwd': avt_bn_acc_doubles(rows, C) doubles;
         'bwd': the avt_bn_bwd_workspace(rows, C) workspace).  Any contents (the producers overwrite their
@@ -317,6 +325,60 @@ class Trunk:
         if not keep:
             tape = None
         return cur, tape
+
+    # ------------------------------------------------------------------ folded inference forward
+    def _conv_bias(self, x, N, H, W, spec: ConvSpec, store: Store, relu: bool, res=None):
+        """relu?(conv(x, w * s) + b (+ res)) in one launch (avt_conv2d_fwd_bias) on the folded operands."""
+        Pq, Qq = conv_out(H, spec.k, spec.stride, spec.pad), conv_out(W, spec.k, spec.stride, spec.pad)
+        y = torch.empty(N, Pq, Qq, spec.cout, device=x.device, dtype=torch.bfloat16)
+        wf, bias = store.folded(spec)
+        ev = ConvProfiler.begin()
+        call("avt_conv2d_fwd_bias", P(x), P(wf), P(y), N, H, W, spec.cp, spec.cout, spec.k, spec.k, spec.stride,
+             spec.pad, spec.kg, P(bias), P(res), int(relu), stream_ptr())
+        ConvProfiler.end(ev, "fwd", 2.0 * N * Pq * Qq * spec.cout * spec.k * spec.k * spec.cin,
+                         2.0 * (x.numel() + wf.numel() + y.numel() * (2 if res is not None else 1)))
+        return y, Pq, Qq
+
+    def forward_folded(self, x: torch.Tensor, store: Store, io: Optional[Dict] = None):
+        """The eval-mode forward with every BatchNorm folded into its conv (store.folded / store.folded_stem: the
+        operands of avt_fold_conv_bn_batched): the stem conv and the fused stem kernel, then per block conv1 with
+        bias + ReLU, the downsample conv with bias, conv2 with bias + residual + ReLU -- 20 conv launches, no
+        avt_bn_apply, no tape.  Returns the layer4 map; io as forward()."""
+        return drive(self.forward_folded_iter(x, store, io))
+
+    def forward_folded_iter(self, x: torch.Tensor, store: Store, io: Optional[Dict] = None):
+        """forward_folded() as a launch generator (see forward_iter)."""
+        N, H, W, _ = x.shape
+        wf, st0 = store.folded_stem(self)
+        H1, W1 = conv_out(H, 7, 2, 3), conv_out(W, 7, 2, 3)
+        c0 = torch.empty(N, H1, W1, 64, device=x.device, dtype=torch.bfloat16)
+        ev = ConvProfiler.begin()
+        call("avt_conv2d_fwd", P(x), P(wf), P(c0), None, N, H, W, self.stem.cp, 64, 7, 7, 2, 3, self.stem.kg,
+             stream_ptr())
+        ConvProfiler.end(ev, "fwd", 2.0 * N * H1 * W1 * 64 * 49 * self.stem.cin,
+                         2.0 * (x.numel() + wf.numel() + c0.numel()))
+        yield
+        H2, W2 = conv_out(H1, 3, 2, 1), conv_out(W1, 3, 2, 1)
+        p0 = torch.empty(N, H2, W2, 64, device=x.device, dtype=torch.bfloat16)
+        idx = torch.empty(N, H2, W2, 64, device=x.device, dtype=torch.uint8)  # the kernel's backward outputs: unused
+        carg = torch.empty_like(p0)
+        call("avt_stem_bn_relu_maxpool_fwd", P(c0), P(st0[0]), P(st0[1]), P(p0), P(idx), P(carg), N, H1, W1, 64,
+             stream_ptr())
+        yield
+        cur, Hc, Wc = p0, H2, W2
+        for bi, blk in enumerate(self.blocks):
+            if io is not None and bi == 6:
+                io["layer4_in"] = cur
+            h1, Ho, Wo = self._conv_bias(cur, N, Hc, Wc, blk["conv1"], store, True)
+            yield
+            res = cur
+            if blk["down"] is not None:
+                res, _, _ = self._conv_bias(cur, N, Hc, Wc, blk["down"], store, False)
+                yield
+            out, _, _ = self._conv_bias(h1, N, Ho, Wo, blk["conv2"], store, True, res=res)
+            yield
+            cur, Hc, Wc = out, Ho, Wo
+        return cur
 
     # ------------------------------------------------------------------ backward
     def _bn_bwd(self, g, y, xc, stats, bn: BNSpec, store: Store, gmask_out=None):

@@ -95,6 +95,19 @@ int avt_copy16(void* dst, const void* src, size_t bytes, int blocks, void* strea
 size_t avt_bn_acc_doubles(long long rows, int C);
 int avt_conv2d_fwd(const void* x, const void* wpack, void* y, double* bn_acc, int N, int H, int W, int Cp, int K,
                    int R, int S, int stride, int pad, int Kg, void* stream);
+/* Inference forward with BatchNorm folded into the conv: y = [relu](conv(x, wpack) + bias[k] (+ residual)).
+ * Replaces, in eval mode, the conv -> bn (-> + identity) (-> relu) groups of BasicBlock.forward
+ * (models/base_models.py:53-69: conv1/bn1/relu at 56-58, conv2/bn2 at 60-61, downsample at 63-64, += and relu at
+ * 66-67) with one launch each: wpack is the image avt_fold_conv_bn_batched writes (w * gamma/sqrt(var + eps)),
+ * bias its beta - mean * scale, so no pre-BN tensor is stored and no avt_bn_apply pass runs.
+ * The arguments are avt_conv2d_fwd's (no statistics accumulator) plus bias (fp32 [K], required), residual (bf16
+ * [N,P,Q,K] or NULL; must not alias y) and relu (0 / 1).  The bias is added to the fp32 accumulators before the
+ * first bf16 rounding in every kernel form; the layer-1 kernel also adds the residual there, the other forms add it
+ * in the store epilogue to the rounded value.  Runs the kernel form avt_conv2d_fwd's planner picks for
+ * the shape; no split-K.  Refuses a NULL bias, K % 64 != 0, C % 32 != 0 (the 7x7 stems keep avt_conv2d_fwd and
+ * avt_stem_bn_relu_maxpool_fwd), more than 9 taps, Kg != R*S*C, strides other than 1 and 2, tensors of 2 GiB or more. */
+int avt_conv2d_fwd_bias(const void* x, const void* wpack, void* y, int N, int H, int W, int Cp, int K, int R, int S,
+                        int stride, int pad, int Kg, const float* bias, const void* residual, int relu, void* stream);
 /* dx[N,H,W,C] = dgrad(dy[N,P,Q,K], wt[C][R*S*K]) (+ add[N,H,W,C] if add != NULL; add may alias dx) */
 int avt_conv2d_dgrad(const void* dy, const void* wt, void* dx, const void* add, int N, int H, int W, int C, int K,
                      int R, int S, int stride, int pad, void* stream);
@@ -443,6 +456,15 @@ size_t avt_pack_desc_bytes(void);
 int avt_pack_conv_weights_batched(const void* descs, int n, long long max_elems, void* stream);
 /* one of its two launches: which = 1 the fwd images, 2 the dgrad images */
 int avt_pack_conv_weights_part(const void* descs, int n, long long max_elems, int which, void* stream);
+/* Fold frozen BatchNorms into the convs in front of them, one launch for many convs (a whole trunk): descs = device
+ * array of n records {const float* w; void* fwd; const float *gamma, *beta, *running_mean, *running_var; float* bias;
+ * int K, RS, C, Cp, Kg, plain; float eps; int pad;} (avt_fold_desc_bytes() each).  With s[k] = gamma[k] *
+ * rsqrt(running_var[k] + eps): fwd = the forward operand image [K][Kg] of avt_pack_conv_weights_batched holding
+ * bf16(w[k,...] * s[k]) (fp32 product, one rounding; padding zero), bias[k] = beta[k] - running_mean[k] * s[k].
+ * plain != 0 (the stems): fwd = the unscaled image and bias = the [2][K] (scale, shift) avt_stem_bn_relu_maxpool_fwd
+ * takes.  max_elems: the largest K*Kg of the records.  Reads nothing it writes; no host sync; deterministic. */
+size_t avt_fold_desc_bytes(void);
+int avt_fold_conv_bn_batched(const void* descs, int n, long long max_elems, void* stream);
 int avt_nchw_to_nhwc_bf16(const float* x, void* y, int N, int C, int H, int W, int Cp, void* stream);
 /* x [N][C][T][H][W] fp32 -> y [(N T)][H][W][Cp] bf16: the 'b c t h w -> (b t) c h w' fold of
  * train_hardway.py:130-131 fused with the NHWC/bf16 conversion */
