@@ -667,7 +667,8 @@ extern "C" int avt_set_wgrad_slots_pct(int pct) {
 // ------------------------------------------------------------------------------------------------
 static inline int conv_out(int in, int k, int st, int pad) { return (in + 2 * pad - k) / st + 1; }
 
-template <int MODE, int WM, int WN, int TM, int TN, int NST, int BK, bool BIAS = false>
+// BIAS: the bias-epilogue instantiations; VIDB picks their Conv3d / long-tap-list form (avt_conv3d_fwd_bias)
+template <int MODE, int WM, int WN, int TM, int TN, int NST, int BK, bool BIAS = false, bool VIDB = false>
 static void launch_pipe_one(const GemmNTParams& p, const NTPipeArgsV& ta0, hipStream_t st) {
   constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
   const int grid = ((p.M + BM - 1) / BM) * (p.Ng / BN);
@@ -681,7 +682,10 @@ static void launch_pipe_one(const GemmNTParams& p, const NTPipeArgsV& ta0, hipSt
     ta.cdiv_hw[k] = make_magic((unsigned)(oh > 0 && ow > 0 ? oh * ow : 1));
     ta.cdiv_ow[k] = make_magic((unsigned)(ow > 0 ? ow : 1));
   }
-  if constexpr (BIAS) {  // avt_conv2d_fwd_bias: a 2-D forward of at most 9 taps
+  if constexpr (BIAS && VIDB) {  // avt_conv3d_fwd_bias: Conv3d rows, up to kMaxTaps taps
+    hipLaunchKernelGGL((conv_nt_pipe_kernel<MODE, WM, WN, TM, TN, NST, BK, true, false, true>), dim3(grid),
+                       dim3(WM * WN * 64), 0, st, p, ta);
+  } else if constexpr (BIAS) {  // avt_conv2d_fwd_bias: a 2-D forward of at most 9 taps
     hipLaunchKernelGGL((conv_nt_pipe_kernel<MODE, WM, WN, TM, TN, NST, BK, false, false, true>), dim3(grid),
                        dim3(WM * WN * 64), 0, st, p, narrow_args(ta));
   } else if (p.IT > 1 || p.OT > 1 || p.KT > 1 || ta.ntaps > 32) {  // Conv3d / the folded 49-tap video stem
@@ -838,6 +842,32 @@ static void launch_glds_bias(const GemmNTParams& p, hipStream_t st) {
   launch_pipe_one<MODE_FWD, WM, WN, TM, TN, NST, BK, true>(p, ta, st);
 }
 
+// ... and for avt_conv3d_fwd_bias: all KT*R*S taps with their temporal displacement, on the kernel's Conv3d form
+template <int WM, int WN, int TM, int TN, int NST, int BK = 32>
+static void launch_glds3d_bias(const GemmNTParams& p, hipStream_t st) {
+  if constexpr (BK == 64) {
+    if (p.IC % 64 != 0) {  // a 64-deep k-tile needs whole 64-channel taps
+      launch_glds3d_bias<2, 2, 2, (WN * TN * 32) / 64, 3, 32>(p, st);
+      return;
+    }
+  }
+  NTPipeArgsV ta{};
+  const int batch = p.M / (p.OT * p.OH * p.OW);
+  ta.act_bytes = (unsigned)((size_t)batch * p.IT * p.IH * p.IW * p.IC * 2);
+  ta.w_bytes = (unsigned)((size_t)p.Ng * p.Kg * 2);
+  ta.ntaps = p.KT * p.R * p.S;
+  for (int kt = 0; kt < p.KT; ++kt)
+    for (int r = 0; r < p.R; ++r)
+      for (int s = 0; s < p.S; ++s) {
+        const int t = (kt * p.R + r) * p.S + s;
+        ta.tap_w[t] = t;
+        ta.tap_dt[t] = kt - p.pad_t;
+        ta.tap_dy[t] = r - p.pad;
+        ta.tap_dx[t] = s - p.pad;
+      }
+  launch_pipe_one<MODE_FWD, WM, WN, TM, TN, NST, BK, true, true>(p, ta, st);
+}
+
 constexpr int kHaloPR = 416;  // patch rows the halo kernels' LDS holds: 256 + 2W + 2 <= 416 -> W <= 79
 
 // 3x3 / stride 1 / pad 1 Conv2d, 64-channel multiples, image width <= 79: the halo-reuse kernel
@@ -955,22 +985,29 @@ static int halo3d_enabled() {
   if (g_halo3d < 0) g_halo3d = getenv("AVT_HALO3D") ? atoi(getenv("AVT_HALO3D")) : 2;
   return g_halo3d;
 }
+// BIAS: the bias-epilogue instantiations of the three tiles (avt_conv3d_fwd_bias); AVT_HALO_TPS2 stays at its
+// default there (wave scheduling only, not a result bit)
+template <bool BIAS = false>
 static bool halo3d_launch(const GemmNTParams& p, hipStream_t st) {
   if (!halo3d_enabled() || p.KT != 3 || p.R != 3 || p.S != 3 || p.stride != 1 || p.pad != 1 || p.pad_t != 1 ||
       p.IT != p.OT || p.IH != p.OH || p.IW != p.OW || p.IC % 64 != 0 || conv_variant() != 1)
     return false;
   if (p.Ng == 64) {  // R3D-18 layer1 (K = 64, W = 112): 256 x 64 on 8 waves of 32 x 64, a 488-row patch (W <= 115)
     if (halo3d_enabled() < 2 || 256 + 2 * p.OW + 2 > 488) return false;
-    launch_halo<MODE_FWD, 8, 1, 1, 2, 3, 488, 4>(p, st);
+    launch_halo<MODE_FWD, 8, 1, 1, 2, 3, 488, 4, BIAS>(p, st);
     return true;
   }
   if (p.Ng % 128 != 0 || 256 + 2 * p.OW + 2 > kHaloPR) return false;
-  if (256 + 2 * p.OW + 2 <= 336 && halo_tps2(p, 3))
-    launch_halo<MODE_FWD, 4, 2, 2, 2, 2, 336, 7>(p, st);  // 256 x 128, 8 waves, W <= 39, two taps per barrier
-  else if (256 + 2 * p.OW + 2 <= 336)
-    launch_halo<MODE_FWD, 4, 2, 2, 2, 3, 336, 4>(p, st);  // 256 x 128, 8 waves, W <= 39
+  if constexpr (!BIAS) {
+    if (256 + 2 * p.OW + 2 <= 336 && halo_tps2(p, 3)) {
+      launch_halo<MODE_FWD, 4, 2, 2, 2, 2, 336, 7>(p, st);  // 256 x 128, 8 waves, W <= 39, two taps per barrier
+      return true;
+    }
+  }
+  if (256 + 2 * p.OW + 2 <= 336)
+    launch_halo<MODE_FWD, 4, 2, 2, 2, 3, 336, 4, BIAS>(p, st);  // 256 x 128, 8 waves, W <= 39
   else
-    launch_halo<MODE_FWD, 4, 2, 2, 2, 2, kHaloPR, 4>(p, st);  // W <= 79: 2 weight stages to fit the 416-row patches
+    launch_halo<MODE_FWD, 4, 2, 2, 2, 2, kHaloPR, 4, BIAS>(p, st);  // W <= 79: 2 weight stages to fit the 416-row patches
   return true;
 }
 
@@ -1516,7 +1553,7 @@ static int conv3d_fwd_impl(const void* x, const void* wpack, void* y, double* bn
               "conv3d_fwd: activation tensors must stay below 2 GiB (32-bit buffer offsets)");
   AVT_REQUIRE(conv_variant() == 1, "conv3d_fwd: needs the LDS-DMA conv kernels (AVT_CONV_VARIANT=1)");
   hipStream_t st = (hipStream_t)stream;
-  if (halo3d_launch(p, st)) return check_launch("conv3d_fwd");
+  if (halo3d_launch<>(p, st)) return check_launch("conv3d_fwd");
   if (K % 128 == 0)
     launch_nt<MODE_FWD, 8, 128, 128>(p, st);
   else
@@ -1527,6 +1564,73 @@ static int conv3d_fwd_impl(const void* x, const void* wpack, void* y, double* bn
 extern "C" int avt_conv3d_fwd(const void* x, const void* wpack, void* y, double* bn_acc, int N, int T, int H, int W,
                               int Cp, int K, int KT, int R, int S, int stride, int pad_t, int pad, void* stream) {
   return conv3d_fwd_impl(x, wpack, y, bn_acc, nullptr, N, T, H, W, Cp, K, KT, R, S, stride, pad_t, pad, stream);
+}
+
+// The planner of avt_conv3d_fwd_bias: conv3d_fwd_impl's choice for the shape under the same knobs -- the halo kernel's
+// three-patch form where halo3d_launch takes it, else launch_nt's tap-gather tile for a Conv3d (or, T = KT = 1: for the
+// 2-D conv of that tap count, the 49-tap folded video stem) -- so a shape keeps the main loop its plain forward runs.
+// As launch_nt_bias, the nt64 / nt128 tile overrides stay at their defaults.
+static void launch_nt3d_bias(const GemmNTParams& p, hipStream_t st) {
+  if (halo3d_launch<true>(p, st)) return;
+  const bool vid = p.IT > 1 || p.OT > 1 || p.KT > 1;
+  if (!vid && p.R * p.S <= 9) {  // a 2-D conv avt_conv2d_fwd_bias takes: its planner
+    launch_nt_bias(p, st);
+    return;
+  }
+  if (!vid && g_nt128_config < 0 && (g_nt64_config < 0 || g_nt64_config == 1) &&
+      use_small_tile(p, p.Ng % 128 == 0 ? 128 : 64)) {
+    if (p.Ng % 128 != 0)
+      launch_glds3d_bias<2, 2, 1, 1, 3>(p, st);  // 64 x 64, k32, 3 stages
+    else
+      launch_glds3d_bias<2, 2, 1, 2, 3>(p, st);  // 64 x 128, k32, 3 stages
+    return;
+  }
+  if (p.Ng % 128 == 0) {
+    if (p.M >= 65536 && (!vid || p.Kg < 3072))
+      launch_glds3d_bias<4, 2, 2, 2, 3>(p, st);  // 256 x 128, 8 waves, k32, 3 stages
+    else
+      launch_glds3d_bias<2, 2, 2, 2, 2, 64>(p, st);  // 128 x 128, k64, 2 stages
+  } else if (vid) {
+    launch_glds3d_bias<2, 2, 2, 1, 4>(p, st);  // 128 x 64, 4 stages
+  } else {
+    launch_glds3d_bias<2, 2, 2, 1, 3>(p, st);  // 128 x 64, 3 stages
+  }
+}
+
+// Conv3d forward with BatchNorm folded in (include/avt.h): y = [relu](conv3d(x, wpack) + bias[k] (+ residual)).
+extern "C" int avt_conv3d_fwd_bias(const void* x, const void* wpack, void* y, int N, int T, int H, int W, int Cp,
+                                   int K, int KT, int R, int S, int stride, int pad_t, int pad, const float* bias,
+                                   const void* residual, int relu, void* stream) {
+  AVT_REQUIRE(x && wpack && y, "conv3d_fwd_bias: null pointer");
+  AVT_REQUIRE(bias, "conv3d_fwd_bias: bias is required (avt_conv3d_fwd is the conv without one)");
+  AVT_REQUIRE(residual == nullptr || residual != y, "conv3d_fwd_bias: residual must not alias y");
+  AVT_REQUIRE(N >= 1 && T >= 1 && H >= 1 && W >= 1, "conv3d_fwd_bias: empty input");
+  AVT_REQUIRE(K >= 64 && K % 64 == 0, "conv3d_fwd_bias: K=%d must be a multiple of 64", K);
+  AVT_REQUIRE(Cp >= 32 && Cp % 32 == 0, "conv3d_fwd_bias: C=%d must be a multiple of 32", Cp);
+  AVT_REQUIRE(KT >= 1 && R >= 1 && S >= 1 && KT * R * S <= kMaxTaps, "conv3d_fwd_bias: at most %d taps", kMaxTaps);
+  AVT_REQUIRE(stride == 1 || stride == 2, "conv3d_fwd_bias: spatial stride must be 1 or 2");
+  AVT_REQUIRE(pad_t >= 0 && pad >= 0, "conv3d_fwd_bias: negative padding");
+  AVT_REQUIRE(conv_variant() == 1, "conv3d_fwd_bias: needs the LDS-DMA conv kernels (AVT_CONV_VARIANT=1)");
+  GemmNTParams p{};
+  p.act = (const bf16_t*)x;
+  p.wmat = (const bf16_t*)wpack;
+  p.out = (bf16_t*)y;
+  p.add = (const bf16_t*)residual;
+  p.bias = bias;
+  p.relu = relu ? 1 : 0;
+  p.IT = T; p.IH = H; p.IW = W; p.IC = Cp;
+  p.OT = T + 2 * pad_t - KT + 1;
+  p.OH = conv_out(H, R, stride, pad);
+  p.OW = conv_out(W, S, stride, pad);
+  AVT_REQUIRE(p.OT >= 1 && H + 2 * pad >= R && W + 2 * pad >= S, "conv3d_fwd_bias: empty output");
+  AVT_REQUIRE((size_t)N * T * H * W * Cp * 2 < (1ull << 31) && (size_t)N * p.OT * p.OH * p.OW * K * 2 < (1ull << 31),
+              "conv3d_fwd_bias: activation tensors must stay below 2 GiB (32-bit buffer offsets)");
+  p.M = N * p.OT * p.OH * p.OW;
+  p.Ng = K;
+  p.Kg = KT * R * S * Cp;
+  p.KT = KT; p.R = R; p.S = S; p.stride = stride; p.pad = pad; p.pad_t = pad_t;
+  launch_nt3d_bias(p, (hipStream_t)stream);
+  return check_launch("conv3d_fwd_bias");
 }
 
 // One parity class (ph, pw) of a spatially strided Conv3d's input gradient on the tap-gather kernel's Conv3d form:

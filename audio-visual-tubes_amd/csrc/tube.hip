@@ -143,6 +143,87 @@ __global__ __launch_bounds__(256) void pack_conv3d_batched_kernel(const Pack3dDe
   }
 }
 
+// Inference fold of the R3D trunk's frozen BatchNorm3d's into the Conv3d's in front of them (avt_fold_conv3d_bn_batched;
+// the 2-D one is misc.hip's fold_conv_bn_batched_kernel): with s[k] = gamma[k] * rsqrt(running_var[k] + eps) (the
+// rsqrt taken through fp64, see the kernel),
+// bn(conv(x, w)) = conv(x, w * s) + (beta - running_mean * s).  One record per conv, blockIdx.y = record, one block per
+// filter row as pack_conv3d_batched_kernel: the fp32 OIDHW row goes through LDS, so reads and writes are both
+// contiguous.  The image is that kernel's (fold-0 layout) -- for the stem record pack_conv3d_kernel's fold-1 layout
+// [K][(r, s)][kt*4 + c], zero padded -- of w[k, ...] * s[k], the product formed in fp32 and rounded to bf16 once;
+// bias[k] = beta[k] - mean[k] * s[k] in two separately rounded operations.  Unlike the 2-D stems, whose BatchNorm stays
+// in the fused max-pool kernel, the R3D stem folds like the rest (FullModel's trunk has no max-pool).  Every output
+// element is written by one thread from its own inputs: deterministic, no atomics.
+struct Fold3dDesc {
+  const float* w;      // fp32 OIDHW [K][C][KT][R][S]
+  bf16_t* out;         // bf16 [K][KT*R*S*C], or (stem) [K][R*S*32]
+  const float* gamma;  // [K]
+  const float* beta;
+  const float* mean;   // running_mean
+  const float* var;    // running_var
+  float* bias;         // [K]
+  int K, C, KT, R, S, stem;
+  float eps;
+  int pad_;
+};
+
+__global__ __launch_bounds__(256) void fold_conv3d_bn_batched_kernel(const Fold3dDesc* __restrict__ descs) {
+#pragma clang fp contract(off)  // beta - mean * s stays two rounded operations (no fma), as documented above
+  extern __shared__ __attribute__((aligned(16))) float row[];
+  const Fold3dDesc d = descs[blockIdx.y];
+  const int RS = d.R * d.S, T = d.KT * RS;
+  const int n = d.C * T;
+  const bool vec = !d.stem && d.C % 8 == 0 && ((((uintptr_t)d.w) | ((uintptr_t)d.out)) & 15) == 0;
+  for (int k = blockIdx.x; k < d.K; k += gridDim.x) {
+    // rsqrt through fp64 (sqrt and divide are correctly rounded there, then one rounding back to fp32): a value any
+    // IEEE host reproduces bit for bit (tests/test_fold3d_pack_gpu.py does, in torch), which the hardware approximation
+    // behind rsqrtf (off by one ulp on about one input in ten) is not
+    const float inv = (float)(1.0 / sqrt((double)(d.var[k] + d.eps)));
+    const float s = __fmul_rn(d.gamma[k], inv);
+    if (threadIdx.x == 0) {  // plain operators: the pragma above covers them (not the bodies of inlined intrinsics)
+      const float ms = d.mean[k] * s;
+      d.bias[k] = d.beta[k] - ms;
+    }
+    const float* wk = d.w + (size_t)k * n;
+    __syncthreads();  // the previous row has been read
+    if (vec) {
+      for (int i = threadIdx.x; i < n / 4; i += blockDim.x)
+        reinterpret_cast<float4*>(row)[i] = reinterpret_cast<const float4*>(wk)[i];
+    } else {
+      for (int i = threadIdx.x; i < n; i += blockDim.x) row[i] = wk[i];
+    }
+    __syncthreads();
+    if (d.stem) {  // [(r, s)][kt*4 + c], 32 channels per (r, s)
+      bf16_t* ok = d.out + (size_t)k * RS * 32;
+      for (int j = threadIdx.x; j < RS * 32; j += blockDim.x) {
+        const int rs = j >> 5, q = j & 31;
+        const int kt = q >> 2, c = q & 3;
+        float v = 0.f;
+        if (kt < d.KT && c < d.C) v = __fmul_rn(row[(c * d.KT + kt) * RS + rs], s);
+        ok[j] = f2bf(v);
+      }
+      continue;
+    }
+    bf16_t* ok = d.out + (size_t)k * n;
+    if (!vec) {
+      for (int j = threadIdx.x; j < n; j += blockDim.x) {
+        const int t = j / d.C, c = j - t * d.C;
+        ok[j] = f2bf(__fmul_rn(row[c * T + t], s));
+      }
+      continue;
+    }
+    for (int j = threadIdx.x; j < n / 8; j += blockDim.x) {  // tap t, channels c .. c + 7: one 16-byte store
+      const int t = (8 * j) / d.C, c = 8 * j - t * d.C;
+      const float* r0 = row + c * T + t;
+      u32x4 o;
+      o.x = pack2(__fmul_rn(r0[0], s), __fmul_rn(r0[T], s));
+      o.y = pack2(__fmul_rn(r0[2 * T], s), __fmul_rn(r0[3 * T], s));
+      o.z = pack2(__fmul_rn(r0[4 * T], s), __fmul_rn(r0[5 * T], s));
+      o.w = pack2(__fmul_rn(r0[6 * T], s), __fmul_rn(r0[7 * T], s));
+      reinterpret_cast<u32x4*>(ok)[j] = o;
+    }
+  }
+}
+
 // out[(b*rep + k)][c] = in[b][c]  (the per-clip audio vector of each of its t frames)
 __global__ __launch_bounds__(256) void repeat_rows_kernel(const float* __restrict__ in, float* __restrict__ out, int B,
                                                           int rep, int C) {
@@ -727,6 +808,18 @@ extern "C" int avt_pack_conv3d_weights_batched(const void* descs, int n, int max
   hipLaunchKernelGGL(pack_conv3d_batched_kernel, dim3(max_k < 512 ? max_k : 512, n), dim3(256),
                      (size_t)max_row * sizeof(float), (hipStream_t)stream, (const Pack3dDesc*)descs);
   return check_launch("pack_conv3d_weights_batched");
+}
+
+extern "C" size_t avt_fold3d_desc_bytes(void) { return sizeof(Fold3dDesc); }
+
+// descs: device array of n avt_fold3d_desc_bytes() records (include/avt.h); one launch folds them all.  max_k = the
+// largest K, max_row = the largest C*KT*R*S (floats; <= 15360: one fp32 filter row in LDS)
+extern "C" int avt_fold_conv3d_bn_batched(const void* descs, int n, int max_k, int max_row, void* stream) {
+  AVT_REQUIRE(descs && n > 0 && max_k > 0, "fold_conv3d_bn_batched: bad arguments");
+  AVT_REQUIRE(max_row > 0 && max_row <= 15360, "fold_conv3d_bn_batched: max_row=%d (<= 15360 floats)", max_row);
+  hipLaunchKernelGGL(fold_conv3d_bn_batched_kernel, dim3(max_k < 512 ? max_k : 512, n), dim3(256),
+                     (size_t)max_row * sizeof(float), (hipStream_t)stream, (const Fold3dDesc*)descs);
+  return check_launch("fold_conv3d_bn_batched");
 }
 
 // Audio de-duplication of the tube step (train_3D.py:128-130 repeats each clip's spectrogram t

@@ -763,6 +763,27 @@ class TrunkEngine(AVEngine):
         call("avt_nhwc_bf16_to_nchw", P(y), P(out), N, C, h * w, stream_ptr())
         return out, tape
 
+    def forward_folded(self, x: torch.Tensor):
+        """forward(training=False) on the folded inference path (a trunk of a FullModel that opted in):
+        Trunk.forward_folded on this engine's own folded operands, refolded (one launch) only when fold_state()
+        has moved.  Returns the layer4 map NCHW fp32."""
+        if not x.is_cuda:
+            raise RuntimeError("avt: inputs must be on the GPU (no CPU path)")
+        cin = 1 if self._modal == "audio" else 3
+        if x.dim() != 4 or x.shape[1] != cin:
+            raise ValueError(f"avt: {self._modal} trunk expects [N,{cin},H,W], got {tuple(x.shape)}")
+        if self.folds is None:
+            self._alloc_folds()
+        state = self.fold_state()
+        if state != self._fold_key:
+            self.fold_trunk(self.trunk)
+        self._fold_key = state
+        y = self.trunk.forward_folded(self._to_nhwc(x, self.trunk.stem.cp), self.store)
+        N, h, w, C = y.shape
+        out = torch.empty(N, C, h, w, device=x.device, dtype=torch.float32)
+        call("avt_nhwc_bf16_to_nchw", P(y), P(out), N, C, h * w, stream_ptr())
+        return out
+
     def backward(self, tape, g_out: torch.Tensor, gflat: torch.Tensor):
         """g_out [N,512,h,w] fp32 (any layout) -> parameter gradients accumulated into gflat; returns the input
         gradient [N,Cin,H,W] fp32 when tape["want_dx"] was set, else None.  gflat None: a "frozen" eval tape."""

@@ -154,8 +154,16 @@ class ResNet(nn.Module):
                                       "BatchNorm only)")
         if need_grad:
             return _TrunkFunction.apply(eng, names, self.training, x, *params)
+        if not self.training and self._folded():
+            return eng.forward_folded(x)
         out, _ = eng.forward(x, self.training)
         return out
+
+    def _folded(self) -> bool:
+        """The folded inference forward for this trunk called on its own: a FullModel's audio trunk follows its
+        parent's ``enable_folded_inference()``; an AVENet's trunks and a standalone trunk keep the unfolded call."""
+        parent = self._avt_parent[0]() if self._avt_parent is not None else None
+        return bool(getattr(parent, "_avt_trunks_follow_fold", False) and getattr(parent, "_avt_folded", False))
 
 
 class _TrunkFunction(torch.autograd.Function):
@@ -586,8 +594,32 @@ class FullModel(nn.Module):
 
         self._flat = FlatStore(self, tube_trainable)
         self._engine = None
+        self._avt_folded = False  # enable_folded_inference(): BatchNorm folded into the convs for eval calls
         self.audnet._adopt(self, "audnet.")
         self.vidnet._adopt(self, "vidnet.")
+
+    _avt_trunks_follow_fold = True  # model.vidnet(video) / model.audnet(x) follow this model's folded flag
+
+    def enable_folded_inference(self):
+        """Opt in to the folded inference forward: in eval mode (this model computes no gradient there) both trunks
+        run with their BatchNorms folded into the conv weights -- the R3D-18 as im2col + 20 conv launches with bias /
+        residual / ReLU epilogues (tube.R3DTrunk.forward_folded), the audio ResNet-18 as AVENet's (Trunk.forward_folded)
+        -- no BatchNorm pass, no per-call weight pack, then the same pool and head, for both audio conventions.  The
+        folded weights are rebuilt, one launch per trunk, whenever a parameter or BN buffer has changed since the
+        last fold (optimizer steps, ``load_state_dict``, a train-mode forward, in-place edits of a buffer); the
+        outputs agree with the unfolded eval forward to bf16 rounding.  Train mode runs exactly as before, as does a
+        model that never calls this.  ``model.vidnet(video)`` and ``model.audnet(x)`` follow this flag.  Idempotent;
+        returns self."""
+        self._avt_folded = True
+        return self
+
+    def invalidate_folded(self):
+        """Force the next folded forward to refold.  Only needed after a write torch cannot see: through
+        ``tensor.data``, or by foreign code holding a raw pointer into the parameters."""
+        for e in (self._engine, self.audnet._avt_engine, self.vidnet._avt_engine):
+            if e is not None:
+                e._fold_key = None
+        return self
 
     def __getstate__(self):
         state = self.__dict__.copy()
@@ -624,5 +656,8 @@ class FullModel(nn.Module):
         train_params = [named[n] for n in self._flat.pnames[:n_train]]
         if torch.is_grad_enabled() and self.training and any(p.requires_grad for p in train_params):
             return _FullModelFunction.apply(eng, True, audio, video, *train_params)
-        out, _ = eng.forward(audio, video, self.training)
+        if not self.training and getattr(self, "_avt_folded", False):
+            out, _ = eng.forward_folded(audio, video)
+        else:
+            out, _ = eng.forward(audio, video, self.training)
         return out["A"], out["logits"]

@@ -18,6 +18,8 @@ that requires grad (``video.grad``, fp32 [b,3,t,H,W], through libavt's ``avt_vid
 attribution over a clip, adversarial or consistency training, a learnable module in front of the trunk -- it works
 with every parameter frozen); ``net.enable_backward(eval_grad=True)`` differentiates an eval-mode trunk (BatchNorm
 frozen on its running statistics, which are read and never updated: ``avt_bn_eval_bwd``).
+Inference: ``net.enable_folded_inference()`` (opt-in) runs eval-mode calls that need no gradient with every BatchNorm3d
+folded into its conv (tube.R3DEngine.forward_folded); inside a FullModel the trunk follows its parent's flag.
 """
 from __future__ import annotations
 
@@ -88,6 +90,30 @@ class ResNet(nn.Module):
         self._avt_backward = False  # enable_backward(): every parameter trainable (standalone modules only)
         self._avt_input_grad = False  # enable_backward(input_grad=True): a video that requires grad gets its gradient
         self._avt_eval_grad = False  # enable_backward(eval_grad=True): eval-mode (running-statistics BN) backward
+        self._avt_folded = False  # enable_folded_inference(): BatchNorm3d folded into the convs for no-grad eval calls
+
+    def enable_folded_inference(self):
+        """Opt in to the folded inference forward: an eval-mode call that needs no gradient (under
+        ``torch.no_grad()``, or with nothing requiring grad) runs with every BatchNorm3d folded into its conv --
+        im2col, 20 conv launches with bias / residual / ReLU epilogues (+ the max-pool), no BatchNorm pass, no
+        per-call weight pack (tube.R3DEngine.forward_folded) -- then the same pooling and ``fc``.  The folded weights
+        are rebuilt, one launch, whenever a parameter or BN buffer has changed since the last fold.  Train mode and
+        calls that take the autograd path (``enable_backward(eval_grad=True)``) run exactly as before, as does a
+        trunk that never calls this.  A trunk owned by a FullModel follows its parent's flag
+        (``FullModel.enable_folded_inference``).  Idempotent; returns self."""
+        self._avt_folded = True
+        return self
+
+    def invalidate_folded(self):
+        """Force the next folded forward to refold (after a write torch cannot see, e.g. through ``tensor.data``)."""
+        if self._avt_engine is not None:
+            self._avt_engine._fold_key = None
+        return self
+
+    def _folded(self) -> bool:
+        if self._avt_parent is not None and self._avt_parent[0]() is not None:
+            return bool(getattr(self._avt_parent[0](), "_avt_folded", False))
+        return bool(getattr(self, "_avt_folded", False))
 
     def _make_layer(self, block, planes, blocks, stride=1):
         downsample = None  # built before the block, as resnet3D.py:169-184 (RNG order)
@@ -181,6 +207,8 @@ class ResNet(nn.Module):
             prefix, flat = "", self._flat_store()
         if self._avt_engine is None or self._avt_engine.flat is not flat:
             self._avt_engine = R3DEngine(flat, prefix, max_pool=not self.no_max_pool)
+        if not self.training and self._folded():
+            return self._avt_engine.forward_folded(x)
         return self._avt_engine.forward(x, self.training)
 
 

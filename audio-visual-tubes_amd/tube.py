@@ -15,6 +15,9 @@ Device data flow (NHWC / NDHWC bf16 activations, fp32 statistics):
       stride 2 on layer2-4's first conv), 1x1x1/s(1,2,2) downsample as avt_conv2d_fwd over the b*t
       frames, BN3d + ReLU (+ residual) by avt_bn_apply --> v [b*t, h, w, 512] = '(b t) h w c'.
   The vidnet's avgpool/fc (resnet3D.py:208-212) feed only the discarded `_` of model.py:33: not run.
+  Folded inference (opt-in, eval + no grad: FullModel.enable_folded_inference): every BatchNorm3d folded
+  into its conv once (avt_fold_conv3d_bn_batched), the trunk then im2col + 20 avt_conv3d_fwd_bias /
+  avt_conv2d_fwd_bias launches with bias (+ residual) (+ ReLU) epilogues -- no BN pass, no per-call weight pack.
 
 Audio de-duplication: given the per-clip spectrogram [b,1,F,T] (what the dataloader yields, before
 train_3D.py:128-130 repeats it), the audio trunk runs once per clip with BN statistics identical to
@@ -183,6 +186,54 @@ class R3DTrunk:
                 call("avt_bn_apply", P(c2), P(s2[0]), P(s2[1]), P(h), None, None, P(out), rows, K, 1, stream_ptr())
             h, H, W = out, Ho, Wo
         return (h, tp) if tape else h
+
+    # ------------------------------------------------------------------ folded inference forward
+    def _conv_bias(self, x, b, T, H, W, spec: Conv3dSpec, store, relu: bool, res=None):
+        """relu?(conv3d(x, w * s) + bias (+ res)) in one launch on the folded operands (store.folded3d)."""
+        Ho, Wo = conv_out(H, spec.k, spec.stride, spec.pad), conv_out(W, spec.k, spec.stride, spec.pad)
+        y = torch.empty(b * T, Ho, Wo, spec.cout, device=x.device, dtype=torch.bfloat16)
+        wf, bias = store.folded3d(spec)
+        ev = ConvProfiler.begin()
+        if spec.stem:  # the 49-tap 7x7 conv over the b*T frames of the 32-channel im2col input
+            call("avt_conv3d_fwd_bias", P(x), P(wf), P(y), b * T, 1, H, W, 32, spec.cout, 1, spec.k, spec.k, spec.stride,
+                 0, spec.pad, P(bias), P(res), int(relu), stream_ptr())
+        elif spec.kt == 1:  # 1x1x1 downsample: a 2-D conv over the b*T frames
+            call("avt_conv2d_fwd_bias", P(x), P(wf), P(y), b * T, H, W, spec.cin, spec.cout, spec.k, spec.k, spec.stride,
+                 spec.pad, spec.kg, P(bias), P(res), int(relu), stream_ptr())
+        else:
+            call("avt_conv3d_fwd_bias", P(x), P(wf), P(y), b, T, H, W, spec.cin, spec.cout, spec.kt, spec.k, spec.k,
+                 spec.stride, spec.pad_t, spec.pad, P(bias), P(res), int(relu), stream_ptr())
+        ConvProfiler.end(ev, "fwd3d", 2.0 * y.numel() * spec.kt * spec.k * spec.k * spec.cin,
+                         2.0 * (x.numel() + wf.numel() + y.numel() * (2 if res is not None else 1)))
+        return y, Ho, Wo
+
+    def forward_folded(self, video: torch.Tensor, store):
+        """The eval-mode forward with every BatchNorm3d folded into its conv (store.folded3d: the operands of
+        avt_fold_conv3d_bn_batched): im2col, the stem conv with bias + ReLU (its BN folds too: no fused max-pool
+        kernel here), the max-pool when the trunk has one, then per block conv1 with bias + ReLU, the downsample with
+        bias, conv2 with bias + residual + ReLU -- 1 + 20 launches (+ 1), no avt_bn_apply, no BN arithmetic, no
+        weight pack, no statistics accumulator, no tape.  Returns forward()'s layer4 map."""
+        video = video.contiguous().float()
+        b, C, T, H, W = video.shape
+        if C != 3:
+            raise ValueError(f"avt: expected video [b,3,t,H,W], got {tuple(video.shape)}")
+        x = torch.empty(b, T, H, W, 32, device=video.device, dtype=torch.bfloat16)
+        call("avt_video_stem_im2col", P(video), P(x), b, C, T, H, W, self.stem.kt, self.stem.pad_t, stream_ptr())
+        h, H, W = self._conv_bias(x, b, T, H, W, self.stem, store, True)
+        del x
+        if self.max_pool:  # resnet3D.py:200-201
+            To, Ho, Wo = (T - 1) // 2 + 1, (H - 1) // 2 + 1, (W - 1) // 2 + 1
+            hp = torch.empty(b * To, Ho, Wo, 64, device=h.device, dtype=torch.bfloat16)
+            call("avt_maxpool3d_fwd", P(h), P(hp), b, T, H, W, 64, stream_ptr())
+            h, T, H, W = hp, To, Ho, Wo
+        for blk in self.blocks:
+            h1, Ho, Wo = self._conv_bias(h, b, T, H, W, blk["conv1"], store, True)
+            res = h
+            if blk["down"] is not None:
+                res, _, _ = self._conv_bias(h, b, T, H, W, blk["down"], store, False)
+            h, _, _ = self._conv_bias(h1, b, T, Ho, Wo, blk["conv2"], store, True, res=res)
+            H, W = Ho, Wo
+        return h
 
     # ------------------------------------------------------------------ backward
     @staticmethod
@@ -377,9 +428,47 @@ def _pack3d(engine, stem_dgrad: bool = False):
                  stream_ptr())
 
 
+def _alloc_folds3d(engine):
+    """The folded operands of the video trunk (first folded forward), kept next to packs3d: per conv the bf16 image
+    of w * bn_scale (the stem in its 32-channel layout) and the fp32 bias, and the device table of all 21 records
+    for avt_fold_conv3d_bn_batched."""
+    import struct
+
+    flat, vid = engine.flat, engine.vid
+    dev = flat.flat.device
+    pairs = [(vid.stem, vid.bn1)]
+    for blk in vid.blocks:
+        pairs += [(blk["conv1"], blk["bn1"]), (blk["conv2"], blk["bn2"])]
+        if blk["down"] is not None:
+            pairs.append((blk["down"], blk["bnd"]))
+    engine.folds3d = {}
+    descs, max_k, max_row = [], 1, 1
+    for spec, bn in pairs:
+        wf = torch.empty(spec.cout, spec.kg, device=dev, dtype=torch.bfloat16)
+        bias = torch.empty(spec.cout, device=dev, dtype=torch.float32)
+        engine.folds3d[spec.name] = (wf, bias)
+        ptrs = [flat.raw(spec.name), wf, flat.raw(bn.prefix + ".weight"), flat.raw(bn.prefix + ".bias"),
+                flat.rawbuf(bn.prefix + ".running_mean"), flat.rawbuf(bn.prefix + ".running_var"), bias]
+        descs.append(struct.pack("<QQQQQQQiiiiiifi", *[t.data_ptr() for t in ptrs], spec.cout, spec.cin, spec.kt,
+                                 spec.k, spec.k, int(spec.stem), AVEngine.BN_EPS, 0))
+        max_k, max_row = max(max_k, spec.cout), max(max_row, spec.cin * spec.kt * spec.k * spec.k)
+    assert len(descs[0]) == int(query("avt_fold3d_desc_bytes"))
+    engine._fold3d_table = torch.frombuffer(bytearray(b"".join(descs)), dtype=torch.uint8).to(dev)
+    engine._fold3d_n, engine._fold3d_max = len(descs), (max_k, max_row)
+
+
+def _fold3d(engine):
+    """One launch: refold the video trunk's BatchNorm3d's into its convs from the flat store (current stream)."""
+    call("avt_fold_conv3d_bn_batched", P(engine._fold3d_table), engine._fold3d_n, *engine._fold3d_max, stream_ptr())
+    engine.fold_launches += 1
+
+
 class _TubeStore(_EngineStore):
     def packed3d(self, spec: Conv3dSpec):
         return self.e.packs3d[spec.name]
+
+    def folded3d(self, spec: Conv3dSpec):
+        return self.e.folds3d[spec.name]
 
     def packed3d_t(self, spec: Conv3dSpec):
         return self.e.packs3d_t[spec.name]
@@ -396,6 +485,7 @@ class TubeEngine(AVEngine):
         self.aud = Trunk("audnet.", "audio")
         self.vid = R3DTrunk("vidnet.")
         self.packs3d: Dict[str, torch.Tensor] = {}
+        self.folds3d = None  # folded inference operands of the video trunk (forward_folded: allocated at first use)
         self.trunks2d = [self.aud]
         self.bn_trunks = [self.aud, self.vid]
 
@@ -408,10 +498,9 @@ class TubeEngine(AVEngine):
         _pack3d(self)
 
     # ----------------------------------------------------------------------------- forward
-    def forward(self, audio: torch.Tensor, video: torch.Tensor, training: bool, with_ce: bool = False,
-                ce_scale: float = 1.0):
-        """audio: [b*t,1,F,T] (folded repeated spectrogram, model.py API) or [b,1,F,T] (one per clip,
-        de-duplicated); video: [b,3,t,H,W].  Returns ({'A', 'logits'[, 'loss', 'dlogits']}, tape)."""
+    @staticmethod
+    def _check_tube_inputs(audio: torch.Tensor, video: torch.Tensor):
+        """-> (B = b*t head rows, rep: how many head rows share one audio row)."""
         if not audio.is_cuda or not video.is_cuda:
             raise RuntimeError("avt: inputs must be on the GPU (no CPU path)")
         if video.dim() != 5 or audio.dim() != 4 or audio.shape[1] != 1:
@@ -425,10 +514,16 @@ class TubeEngine(AVEngine):
             rep = t
         else:
             raise ValueError(f"avt: audio batch {audio.shape[0]} must be b*t={B} (folded) or b={b} (per clip)")
+        return B, rep
+
+    def forward(self, audio: torch.Tensor, video: torch.Tensor, training: bool, with_ce: bool = False,
+                ce_scale: float = 1.0):
+        """audio: [b*t,1,F,T] (folded repeated spectrogram, model.py API) or [b,1,F,T] (one per clip,
+        de-duplicated); video: [b,3,t,H,W].  Returns ({'A', 'logits'[, 'loss', 'dlogits']}, tape)."""
+        B, rep = self._check_tube_inputs(audio, video)
         self.pack_weights()
         if training:
             self.flat.nbt.add_(1)
-        dev = video.device
         xa = self._to_nhwc(audio, 1)
         self.aud.bn_rep = rep
         try:
@@ -436,6 +531,31 @@ class TubeEngine(AVEngine):
         finally:
             self.aud.bn_rep = 1
         v = self.vid.forward(video, self.store, training)
+        return self._tube_head(a, tape_a, v, B, rep, training, with_ce, ce_scale)
+
+    def forward_folded(self, audio: torch.Tensor, video: torch.Tensor):
+        """forward(training=False) on the folded inference path (FullModel.enable_folded_inference): the audio trunk
+        as Trunk.forward_folded (bn_rep plays no part in eval), the video trunk as R3DTrunk.forward_folded, then the
+        same pool + head -- no BatchNorm launch, no per-call BN arithmetic, no weight pack.  The folded operands of
+        both trunks are rebuilt (one launch per trunk) only when fold_state() has moved since they were built.
+        Returns forward()'s (out, None)."""
+        B, rep = self._check_tube_inputs(audio, video)
+        if self.folds is None:
+            self._alloc_folds()
+        if self.folds3d is None:
+            _alloc_folds3d(self)
+        state = self.fold_state()
+        if state != self._fold_key:
+            self.fold_trunk(self.aud)
+            _fold3d(self)
+        self._fold_key = state
+        a = self.aud.forward_folded(self._to_nhwc(audio, 1), self.store)
+        v = self.vid.forward_folded(video, self.store)
+        return self._tube_head(a, None, v, B, rep, False, False, 1.0)
+
+    def _tube_head(self, a, tape_a, v, B, rep, training, with_ce, ce_scale):
+        """AdaptiveMaxPool2d + normalize of the audio map, the hard-way head on (v, an) and the forward's tape."""
+        dev = v.device
         _, h, w, C = v.shape
         Pn = h * w
         Ba = a.shape[0]
@@ -531,6 +651,7 @@ class R3DEngine(AVEngine):
     def _setup_trunks(self):
         self.vid = R3DTrunk(self._prefix, self._max_pool)
         self.packs3d: Dict[str, torch.Tensor] = {}
+        self.folds3d = None  # folded inference operands of the video trunk (forward_folded: allocated at first use)
         self.trunks2d = []
         self.bn_trunks = [self.vid]
 
@@ -564,6 +685,26 @@ class R3DEngine(AVEngine):
                       stem_dgrad=input_grad)
             return torch.addmm(bias, feat, w.t()), tp
         v = self.vid.forward(video, self.store, training)  # [(b t), h, w, 512] bf16
+        feat = v.view(b, -1, v.shape[-1]).float().mean(1)  # AdaptiveAvgPool3d((1,1,1)) + flatten
+        return torch.addmm(bias, feat, w.t())  # nn.Linear (resnet3D.py:212)
+
+    def forward_folded(self, video: torch.Tensor):
+        """forward(training=False) on the folded inference path (resnet3D.ResNet.enable_folded_inference):
+        R3DTrunk.forward_folded, then the same mean + addmm.  The folded operands are rebuilt (one launch) only
+        when fold_state() has moved since they were built."""
+        if not video.is_cuda:
+            raise RuntimeError("avt: inputs must be on the GPU (no CPU path)")
+        if video.dim() != 5:
+            raise ValueError(f"avt: expected video [b,3,t,H,W], got {tuple(video.shape)}")
+        if self.folds3d is None:
+            _alloc_folds3d(self)
+        state = self.fold_state()
+        if state != self._fold_key:
+            _fold3d(self)
+        self._fold_key = state
+        b = video.shape[0]
+        w, bias = self.flat.raw(self._prefix + "fc.weight"), self.flat.raw(self._prefix + "fc.bias")
+        v = self.vid.forward_folded(video, self.store)  # [(b t), h, w, 512] bf16
         feat = v.view(b, -1, v.shape[-1]).float().mean(1)  # AdaptiveAvgPool3d((1,1,1)) + flatten
         return torch.addmm(bias, feat, w.t())  # nn.Linear (resnet3D.py:212)
 

@@ -194,6 +194,31 @@ int avt_conv_stem_dgrad(const void* gy, const float* w, float* gx, int N, int H,
  * T' = T + 2*pad_t - KT + 1, spatial stride 1 or 2; Cp % 32 == 0; KT*R*S <= 27; bn_acc as conv2d_fwd */
 int avt_conv3d_fwd(const void* x, const void* wpack, void* y, double* bn_acc, int N, int T, int H, int W, int Cp,
                    int K, int KT, int R, int S, int stride, int pad_t, int pad, void* stream);
+/* Inference Conv3d with BatchNorm3d folded in: y = [relu](conv3d(x, wpack) + bias[k] (+ residual)).  Replaces, in eval
+ * mode, the conv -> bn (-> + residual) (-> relu) groups of the R3D-18 (models/resnet3D.py: BasicBlock.forward 45-61,
+ * the stem conv1/bn1/relu of ResNet.forward 198-200) with one launch each: wpack is the image
+ * avt_fold_conv3d_bn_batched writes, bias its beta - mean * scale; no pre-BN tensor is stored, no avt_bn_apply runs.
+ * The arguments are avt_conv3d_fwd's without the statistics accumulator, plus bias (fp32 [K], required), residual
+ * (bf16 [N,T',P,Q,K] or NULL; must not alias y) and relu (0 / 1).  The fp32 bias joins the fp32 accumulators before
+ * the first bf16 rounding; residual and ReLU are applied in the store to the rounded value.  Runs the
+ * kernel form avt_conv3d_fwd's planner picks for the shape (the halo kernel's three-patch form, else the tap-gather
+ * kernel's Conv3d form; a T = KT = 1 conv of at most 9 taps goes where avt_conv2d_fwd_bias sends it).  The folded
+ * 7x7x7 video stem is the KT = 1, 7x7 / stride 2 conv over the N*T frames of avt_video_stem_im2col's 32-channel
+ * input (49 taps).  Refuses a NULL bias, an aliasing residual, K % 64 != 0, Cp % 32 != 0, more than 49 taps, strides
+ * other than 1 and 2, tensors of 2 GiB or more, and a build without the LDS-DMA conv variant. */
+int avt_conv3d_fwd_bias(const void* x, const void* wpack, void* y, int N, int T, int H, int W, int Cp, int K, int KT,
+                        int R, int S, int stride, int pad_t, int pad, const float* bias, const void* residual,
+                        int relu, void* stream);
+/* Fold frozen BatchNorm3d's into the Conv3d's in front of them, one launch for the whole R3D trunk: descs = device
+ * array of n records {const float* w; void* out; const float *gamma, *beta, *running_mean, *running_var; float* bias;
+ * int K, C, KT, R, S, stem; float eps; int pad;} (avt_fold3d_desc_bytes() each), w fp32 OIDHW.  With s[k] = gamma[k] *
+ * rsqrt(running_var[k] + eps) (the sum in fp32, its rsqrt as (float)(1 / sqrt((double)sum)): reproducible on any IEEE
+ * host): out[k][t*C + c] = bf16(w[k][c][t] * s[k]) (t = (kt, r, s); the layout of
+ * avt_pack_conv3d_weights_batched; fp32 product, one rounding), or for a stem record (C <= 4, KT <= 8) the fold-1
+ * layout [K][(r,s)][kt*4+c] of avt_pack_conv3d_weight, zero padded; bias[k] = beta[k] - running_mean[k] * s[k].
+ * max_k = the largest K, max_row = the largest C*KT*R*S (<= 15360).  No host sync; deterministic. */
+size_t avt_fold3d_desc_bytes(void);
+int avt_fold_conv3d_bn_batched(const void* descs, int n, int max_k, int max_row, void* stream);
 /* R3D stem input: x fp32 NCDHW [N][C<=4][T][H][W] -> bf16 [N][T][H][W][32], channel kt*4+c = x[c][t+kt-pad_t]
  * (zero outside the clip / for c >= C / channels >= 4*KT) */
 int avt_video_stem_im2col(const float* x, void* out, int N, int C, int T, int H, int W, int KT, int pad_t,
