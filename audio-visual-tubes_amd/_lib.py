@@ -103,6 +103,7 @@ SIGNATURES = {
     "avt_bn_finalize_rep": (_I, [_P, _L, _L, _I, _P, _P, _P, _P, _F, _F, _P, _P, _P, _P, _P]),
     "avt_conv3d_fwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "avt_conv3d_fwd_bias": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P]),
+    "avt_conv_fwd_plan": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "avt_fold3d_desc_bytes": (_Z, []),
     "avt_fold_conv3d_bn_batched": (_I, [_P, _I, _I, _I, _P]),
     "avt_video_stem_im2col": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),

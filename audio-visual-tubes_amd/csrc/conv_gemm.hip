@@ -11,6 +11,7 @@
 // wgrad ("TN"): both operands pixel-major in LDS, fragments by ds_read_b64_tr_b16 (hardware transpose).
 // MFMA: v_mfma_f32_32x32x16_bf16, 4 waves (2x2) per 256-thread block, register-staged double buffer.
 #include "avt_common.h"
+#include "avt_tuning.h"  // the knobs and avt_conv_fwd_plan defined here
 
 namespace avt {
 
@@ -461,7 +462,7 @@ static int stem_wgrad_enabled() {
 }
 
 static int g_nt64_config = -1;  // tile config of the pipelined NT kernel for 64-wide GEMM N (A/B knob; -1 auto)
-static int g_nt128_config = -1; // ... and for GEMM N % 128 == 0 (-1: by GEMM M, see launch_nt)
+static int g_nt128_config = -1; // ... and for GEMM N % 128 == 0 (-1: by GEMM M, see plan_nt)
 static int g_wgrad_blocks = 0;     // wgrad split-K: 0 = wave model (wgrad_plan), >0 = fixed block target
 static int g_wgrad_min_kt = 4;
 // largest split count that goes through a slab (deterministic: split partials summed in split order); beyond it
@@ -667,6 +668,11 @@ extern "C" int avt_set_wgrad_slots_pct(int pct) {
 // ------------------------------------------------------------------------------------------------
 static inline int conv_out(int in, int k, int st, int pad) { return (in + 2 * pad - k) / st + 1; }
 
+// the store epilogue of a fwd/dgrad launch (the values of avt_conv_fwd_plan's `epi`, include/avt_tuning.h): plain
+// (BN statistics, add, BN-backward), the bias epilogue on the 2-D kernels' narrow argument form (at most 9 taps),
+// the bias epilogue on the Conv3d / long-tap-list form
+enum { EPI_PLAIN = 0, EPI_BIAS2D = 1, EPI_BIAS3D = 2 };
+
 // BIAS: the bias-epilogue instantiations; VIDB picks their Conv3d / long-tap-list form (avt_conv3d_fwd_bias)
 template <int MODE, int WM, int WN, int TM, int TN, int NST, int BK, bool BIAS = false, bool VIDB = false>
 static void launch_pipe_one(const GemmNTParams& p, const NTPipeArgsV& ta0, hipStream_t st) {
@@ -701,30 +707,34 @@ static void launch_pipe_one(const GemmNTParams& p, const NTPipeArgsV& ta0, hipSt
   }
 }
 
-// Builds the tap list(s) and launches: fwd / stride-1 dgrad in one launch; a stride-2 dgrad as
-// four parity-class launches, each walking only its class's taps.
-template <int MODE, int WM, int WN, int TM, int TN, int NST = 4, int BK = 32>
+// The tap list of a forward or a stride-1 dgrad: all KT*R*S taps in weight order, each displaced by
+// (kt, r, s) - pad (forward) or pad - (kt, r, s) (dgrad).  A 2-D conv is KT = 1, pad_t = 0.
+static void fill_taps(NTPipeArgsV& ta, const GemmNTParams& p, int mode) {
+  const int sgn = mode == MODE_FWD ? 1 : -1;
+  ta.ntaps = p.KT * p.R * p.S;
+  for (int kt = 0; kt < p.KT; ++kt)
+    for (int r = 0; r < p.R; ++r)
+      for (int s = 0; s < p.S; ++s) {
+        const int t = (kt * p.R + r) * p.S + s;
+        ta.tap_w[t] = t;
+        ta.tap_dt[t] = sgn * (kt - p.pad_t);
+        ta.tap_dy[t] = sgn * (r - p.pad);
+        ta.tap_dx[t] = sgn * (s - p.pad);
+      }
+}
+
+// Builds the tap list(s) and launches: fwd / stride-1 dgrad in one launch (EPI: on the plain or a bias-epilogue
+// instantiation); a stride-2 dgrad as four parity-class launches, each walking only its class's taps.
+// BK = 64 needs whole 64-channel taps (IC % 64 == 0: plan_nt sees to it).
+template <int MODE, int WM, int WN, int TM, int TN, int NST, int BK, int EPI = EPI_PLAIN>
 static void launch_glds(const GemmNTParams& p, hipStream_t st) {
-  if (BK == 64 && p.IC % 64 != 0) {  // a 64-deep k-tile needs whole 64-channel taps
-    launch_glds<MODE, 2, 2, 2, (WN * TN * 32) / 64, 3, 32>(p, st);  // 4-wave k32 tile of the same width
-    return;
-  }
   NTPipeArgsV ta{};
   const int batch = p.M / (p.OT * p.OH * p.OW);
   ta.act_bytes = (unsigned)((size_t)batch * p.IT * p.IH * p.IW * p.IC * 2);
   ta.w_bytes = (unsigned)((size_t)p.Ng * p.Kg * 2);
   if (MODE == MODE_FWD || p.stride == 1) {
-    ta.ntaps = p.KT * p.R * p.S;
-    for (int kt = 0; kt < p.KT; ++kt)
-      for (int r = 0; r < p.R; ++r)
-        for (int s = 0; s < p.S; ++s) {
-          const int t = (kt * p.R + r) * p.S + s;
-          ta.tap_w[t] = t;
-          ta.tap_dt[t] = MODE == MODE_FWD ? kt - p.pad_t : p.pad_t - kt;
-          ta.tap_dy[t] = MODE == MODE_FWD ? r - p.pad : p.pad - r;
-          ta.tap_dx[t] = MODE == MODE_FWD ? s - p.pad : p.pad - s;
-        }
-    launch_pipe_one<MODE, WM, WN, TM, TN, NST, BK>(p, ta, st);
+    fill_taps(ta, p, MODE);
+    launch_pipe_one<MODE, WM, WN, TM, TN, NST, BK, EPI != EPI_PLAIN, EPI == EPI_BIAS3D>(p, ta, st);
     return;
   }
   ta.cls = 1;
@@ -818,57 +828,11 @@ static void launch_glds(const GemmNTParams& p, hipStream_t st) {
       }
 }
 
-// launch_glds's forward branch for the bias-epilogue instantiations (avt_conv2d_fwd_bias): all R*S taps, one launch
-template <int WM, int WN, int TM, int TN, int NST, int BK = 32>
-static void launch_glds_bias(const GemmNTParams& p, hipStream_t st) {
-  if constexpr (BK == 64) {
-    if (p.IC % 64 != 0) {  // a 64-deep k-tile needs whole 64-channel taps
-      launch_glds_bias<2, 2, 2, (WN * TN * 32) / 64, 3, 32>(p, st);
-      return;
-    }
-  }
-  NTPipeArgsV ta{};
-  const int batch = p.M / (p.OH * p.OW);
-  ta.act_bytes = (unsigned)((size_t)batch * p.IH * p.IW * p.IC * 2);
-  ta.w_bytes = (unsigned)((size_t)p.Ng * p.Kg * 2);
-  ta.ntaps = p.R * p.S;
-  for (int r = 0; r < p.R; ++r)
-    for (int s = 0; s < p.S; ++s) {
-      const int t = r * p.S + s;
-      ta.tap_w[t] = t;
-      ta.tap_dy[t] = r - p.pad;
-      ta.tap_dx[t] = s - p.pad;
-    }
-  launch_pipe_one<MODE_FWD, WM, WN, TM, TN, NST, BK, true>(p, ta, st);
-}
-
-// ... and for avt_conv3d_fwd_bias: all KT*R*S taps with their temporal displacement, on the kernel's Conv3d form
-template <int WM, int WN, int TM, int TN, int NST, int BK = 32>
-static void launch_glds3d_bias(const GemmNTParams& p, hipStream_t st) {
-  if constexpr (BK == 64) {
-    if (p.IC % 64 != 0) {  // a 64-deep k-tile needs whole 64-channel taps
-      launch_glds3d_bias<2, 2, 2, (WN * TN * 32) / 64, 3, 32>(p, st);
-      return;
-    }
-  }
-  NTPipeArgsV ta{};
-  const int batch = p.M / (p.OT * p.OH * p.OW);
-  ta.act_bytes = (unsigned)((size_t)batch * p.IT * p.IH * p.IW * p.IC * 2);
-  ta.w_bytes = (unsigned)((size_t)p.Ng * p.Kg * 2);
-  ta.ntaps = p.KT * p.R * p.S;
-  for (int kt = 0; kt < p.KT; ++kt)
-    for (int r = 0; r < p.R; ++r)
-      for (int s = 0; s < p.S; ++s) {
-        const int t = (kt * p.R + r) * p.S + s;
-        ta.tap_w[t] = t;
-        ta.tap_dt[t] = kt - p.pad_t;
-        ta.tap_dy[t] = r - p.pad;
-        ta.tap_dx[t] = s - p.pad;
-      }
-  launch_pipe_one<MODE_FWD, WM, WN, TM, TN, NST, BK, true, true>(p, ta, st);
-}
-
 constexpr int kHaloPR = 416;  // patch rows the halo kernels' LDS holds: 256 + 2W + 2 <= 416 -> W <= 79
+// the patch of a 128-row tile fits 168 rows (W <= 19: the 4-wave 128 x 128 tile at two blocks per CU), that of a
+// 256-row tile 336 (W <= 39: room for a third weight stage)
+static bool halo128_fits(const GemmNTParams& p) { return 128 + 2 * p.OW + 2 <= 168; }
+static bool halo256_short(const GemmNTParams& p) { return 256 + 2 * p.OW + 2 <= 336; }
 
 // 3x3 / stride 1 / pad 1 Conv2d, 64-channel multiples, image width <= 79: the halo-reuse kernel
 static bool halo_eligible(const GemmNTParams& p) {
@@ -880,7 +844,7 @@ static bool halo_eligible(const GemmNTParams& p) {
   // W <= 19 (layer3/4): 4-wave 128x128; W <= 79 (layer2): 8-wave 256x128 (measured with the unrolled tap
   // loop: audio layer2 +6-10 % at B=128 and +28 % at B=32 over the tap gather, vision layer2 +0-6 %)
   static const int l2 = getenv("AVT_HALO_L2") ? atoi(getenv("AVT_HALO_L2")) : 1;  // A/B: 0 = layer2 on the tap gather
-  return p.Ng % 128 == 0 && (128 + 2 * p.OW + 2 <= 168 || (l2 && 256 + 2 * p.OW + 2 <= kHaloPR));
+  return p.Ng % 128 == 0 && (halo128_fits(p) || (l2 && 256 + 2 * p.OW + 2 <= kHaloPR));
 }
 
 // Small GEMMs (a few clips per GPU: BASELINE configs[2] runs 32 per GPU): a tile grid that leaves
@@ -970,10 +934,13 @@ static void launch_halo(const GemmNTParams& p, hipStream_t st, int ksplit = 1, f
 // (profiles/r6_ab_tps2_b128.txt) and +-2 % on the Conv3d shapes (r6_conv3d_halo.txt): off by default.
 // avt_set_halo_tps2 / env AVT_HALO_TPS2 (0 default, 1 on; -1 back to the environment)
 static int g_halo_tps2 = -1;
-static int halo_tps2(const GemmNTParams& p, int vt = 1) {
+static int halo_tps2() {
   if (g_halo_tps2 < 0) g_halo_tps2 = getenv("AVT_HALO_TPS2") ? atoi(getenv("AVT_HALO_TPS2")) : 0;
+  return g_halo_tps2;
+}
+static bool halo_tps2_shape(const GemmNTParams& p, int vt = 1) {  // vt: virtual chunks per 64 channels (Conv3d: 3)
   const int nv = p.IC / 64 * vt;
-  return g_halo_tps2 && p.IC % 64 == 0 && nv % 2 == 0 && nv >= 8;
+  return p.IC % 64 == 0 && nv % 2 == 0 && nv >= 8;
 }
 
 // Conv3d 3x3x3 / stride 1 / pad 1 with T' = T on the halo kernel's three-patch form: the R3D-18 layer2-4 convs (N %
@@ -985,44 +952,13 @@ static int halo3d_enabled() {
   if (g_halo3d < 0) g_halo3d = getenv("AVT_HALO3D") ? atoi(getenv("AVT_HALO3D")) : 2;
   return g_halo3d;
 }
-// BIAS: the bias-epilogue instantiations of the three tiles (avt_conv3d_fwd_bias); AVT_HALO_TPS2 stays at its
-// default there (wave scheduling only, not a result bit)
-template <bool BIAS = false>
-static bool halo3d_launch(const GemmNTParams& p, hipStream_t st) {
+static bool halo3d_eligible(const GemmNTParams& p) {
   if (!halo3d_enabled() || p.KT != 3 || p.R != 3 || p.S != 3 || p.stride != 1 || p.pad != 1 || p.pad_t != 1 ||
       p.IT != p.OT || p.IH != p.OH || p.IW != p.OW || p.IC % 64 != 0 || conv_variant() != 1)
     return false;
-  if (p.Ng == 64) {  // R3D-18 layer1 (K = 64, W = 112): 256 x 64 on 8 waves of 32 x 64, a 488-row patch (W <= 115)
-    if (halo3d_enabled() < 2 || 256 + 2 * p.OW + 2 > 488) return false;
-    launch_halo<MODE_FWD, 8, 1, 1, 2, 3, 488, 4, BIAS>(p, st);
-    return true;
-  }
-  if (p.Ng % 128 != 0 || 256 + 2 * p.OW + 2 > kHaloPR) return false;
-  if constexpr (!BIAS) {
-    if (256 + 2 * p.OW + 2 <= 336 && halo_tps2(p, 3)) {
-      launch_halo<MODE_FWD, 4, 2, 2, 2, 2, 336, 7>(p, st);  // 256 x 128, 8 waves, W <= 39, two taps per barrier
-      return true;
-    }
-  }
-  if (256 + 2 * p.OW + 2 <= 336)
-    launch_halo<MODE_FWD, 4, 2, 2, 2, 3, 336, 4, BIAS>(p, st);  // 256 x 128, 8 waves, W <= 39
-  else
-    launch_halo<MODE_FWD, 4, 2, 2, 2, 2, kHaloPR, 4, BIAS>(p, st);  // W <= 79: 2 weight stages to fit the 416-row patches
-  return true;
-}
-
-// the 4-wave 128 x 128 halo tile by weight-ring depth (avt_set_halo_stages / AVT_HALO_NST): 2 stages (80 KB
-// LDS, 2 blocks per CU; one 16 KiB weight stage in flight behind each step's 16 MFMAs per wave) or 3-5
-// (96-128 KB, 1 block per CU; NSTB-1 stages in flight)
-template <int MODE>
-static void launch_halo128(const GemmNTParams& p, hipStream_t st, int ks = 1, float* part = nullptr,
-                           int* cnt = nullptr) {
-  switch (halo_nst()) {
-    case 3: launch_halo<MODE, 2, 2, 2, 2, 3, 168>(p, st, ks, part, cnt); break;
-    case 4: launch_halo<MODE, 2, 2, 2, 2, 4, 168>(p, st, ks, part, cnt); break;
-    case 5: launch_halo<MODE, 2, 2, 2, 2, 5, 168>(p, st, ks, part, cnt); break;
-    default: launch_halo<MODE, 2, 2, 2, 2, 2, 168>(p, st, ks, part, cnt); break;
-  }
+  // R3D-18 layer1 (K = 64, W = 112): a 488-row patch (W <= 115)
+  if (p.Ng == 64) return halo3d_enabled() >= 2 && 256 + 2 * p.OW + 2 <= 488;
+  return p.Ng % 128 == 0 && 256 + 2 * p.OW + 2 <= kHaloPR;
 }
 
 // ---- split-K for the 128 x 128 halo tile (layer3/4 at a few clips per GPU) ----
@@ -1040,7 +976,7 @@ struct SplitWs {
   int counters;
 };
 static bool halo_splitk_shape(const GemmNTParams& p) {
-  return halo_eligible(p) && conv_variant() == 1 && p.Ng % 128 == 0 && 128 + 2 * p.OW + 2 <= 168 &&
+  return halo_eligible(p) && conv_variant() == 1 && p.Ng % 128 == 0 && halo128_fits(p) &&
          p.bx == nullptr;
 }
 static int halo_splitk(const GemmNTParams& p) {
@@ -1075,9 +1011,16 @@ static bool c64_eligible(const GemmNTParams& p) {
          p.IW == p.OW && 256 + 2 * p.OW + 2 <= c64::PRMAX && p.bx == nullptr && (p.add == nullptr || p.add != p.out);
 }
 
-// BIAS: the bias-epilogue instantiation (avt_conv2d_fwd_bias; conv_c64_kernel's ADD 3, on the default 8-wave form)
+// 8-wave blocks (two waves per SIMD; default): layer-1 fwd/dgrad 519/630 -> 638/762 TFLOP/s (vision), step
+// 12.61 k -> 12.86 k clips/s in the same-box A/B; AVT_C64_WAVES=4: the 4-wave form
+static int c64_waves() {
+  static const int w = getenv("AVT_C64_WAVES") && atoi(getenv("AVT_C64_WAVES")) == 4 ? 4 : 8;
+  return w;
+}
+
+// BIAS: the bias-epilogue instantiation (avt_conv2d_fwd_bias; conv_c64_kernel's ADD 3, 8 waves only)
 template <int MODE, bool BIAS = false>
-static void launch_c64(const GemmNTParams& p, hipStream_t st) {
+static void launch_c64(const GemmNTParams& p, hipStream_t st, int waves) {
   C64Args ca{};
   const int batch = p.M / (p.OH * p.OW);
   ca.act_bytes = (unsigned)((size_t)batch * p.IH * p.IW * 64 * 2);
@@ -1111,9 +1054,7 @@ static void launch_c64(const GemmNTParams& p, hipStream_t st) {
     hipLaunchKernelGGL((conv_c64_kernel<MODE_FWD, 3, 8>), dim3(grid), dim3(512), 0, st, p, ca);
     return;
   }
-  // 8-wave blocks (two waves per SIMD; default): layer-1 fwd/dgrad 519/630 -> 638/762 TFLOP/s (vision), step
-  // 12.61 k -> 12.86 k clips/s in the same-box A/B; AVT_C64_WAVES=4: the 4-wave form
-  static const int w8 = !(getenv("AVT_C64_WAVES") && atoi(getenv("AVT_C64_WAVES")) == 4);
+  const bool w8 = waves != 4;
   if constexpr (MODE == MODE_DGRAD) {
     if (p.add != nullptr && p.amask != nullptr) {
       if (w8)
@@ -1136,103 +1077,247 @@ static void launch_c64(const GemmNTParams& p, hipStream_t st) {
     hipLaunchKernelGGL((conv_c64_kernel<MODE, 0>), dim3(grid), dim3(256), 0, st, p, ca);
 }
 
-template <int MODE, int CVEC, int BM, int BN>
-static void launch_nt(const GemmNTParams& p, hipStream_t st, const SplitWs* ws = nullptr) {
-  if (CVEC == 8 && c64_eligible(p)) {
-    launch_c64<MODE>(p, st);
-    return;
+// ---- the fwd/dgrad plan: kernel family and tile of a call (plan_nt), and its launch (launch_plan) ----
+enum { NT_C64 = 0, NT_HALO = 1, NT_HALO3D = 2, NT_GATHER = 3, NT_REG = 4, NT_STEM = 5 };  // avt_conv_fwd_plan's family
+struct NtPlan {
+  int family;
+  int wm, wn, tm, tn;  // waves per block (rows x columns), 32 x 32 MFMA tiles per wave: a wm*tm*32 x wn*tn*32 tile
+  int nst;             // LDS ring stages (halo: of the weight ring)
+  int kp;              // tap gather, register-staged: k-tile depth BK; halo: patch rows PRMAX
+  int opt;             // conv_halo_kernel's OPT
+  int ksplit;
+  int epi;             // the epilogue instantiated: EPI_PLAIN, or the bias form the shape takes
+};
+static const SplitWs kAnySplitWs{nullptr, nullptr, 1ll << 62, 1 << 30};  // planning only: every split-K plan fits
+
+// Kernel family and tile of a forward (mode MODE_FWD) or 2-D dgrad call.  `ws`: the split-K workspace passed, if any.
+// c64, then split-K, then the 64-row tiles of a small GEMM, then the halo tiles, then the tap gather by GEMM size;
+// the register-staged gemm_nt_kernel for the stems' C = 4 / 1 and under avt_set_conv_variant(0).
+static NtPlan plan_nt(const GemmNTParams& p, int mode, int epi, const SplitWs* ws) {
+  const bool vid = p.IT > 1 || p.OT > 1 || p.KT > 1;
+  const bool bias = epi != EPI_PLAIN;
+  // a bias epilogue is instantiated on the Conv3d / long-tap-list argument form only for what needs it: a 2-D conv
+  // of at most 9 taps takes the narrow form whichever entry point it came through
+  if (bias) epi = vid || p.R * p.S > 9 ? EPI_BIAS3D : EPI_BIAS2D;
+  // The canonical tile of a bias epilogue: the knobs that only trade ring depth or wave layout (halo stages, halo8
+  // form / nst / tps2, AVT_C64_WAVES, the nt64 / nt128 tile overrides) stay at their defaults there -- they do not
+  // change a result bit, and each would cost another instantiation.  Everything below reads them from here.
+  const int nst128 = bias ? 2 : halo_nst(), nst64 = bias ? 3 : halo_small_nst();
+  const int form8 = bias ? 0 : halo8_form(), nst8 = bias ? 3 : halo8_nst();
+  const bool tps2 = !bias && halo_tps2();
+  const int c64w = bias ? 8 : c64_waves();
+  const int cfg64 = bias ? -1 : g_nt64_config, cfg128 = bias ? -1 : g_nt128_config;
+  const auto ring = [](int nst) { return nst >= 3 && nst <= 5 ? nst : 2; };
+  const auto tile = [epi](int family, int wm, int wn, int tm, int tn, int nst, int kp, int opt = 0, int ksplit = 1) {
+    return NtPlan{family, wm, wn, tm, tn, nst, kp, opt, ksplit, epi};
+  };
+
+  if (!bias && mode == MODE_FWD && !vid && (p.IC == 4 || p.IC == 1) && stem_enabled() && p.Ng == 64 && p.R == 7 &&
+      p.S == 7 && p.stride == 2 && p.pad == 3 && (p.IC == 4 ? stem_fits<4>(p.OW) : stem_fits<1>(p.OW)))
+    return tile(NT_STEM, kStemNW, 1, 0, 0, 0, 0);  // conv_stem_fwd_kernel: kStemNW wave tiles per block
+  if (p.IC % 32 != 0 || conv_variant() != 1)  // 128 x 128 or 128 x 64, double-buffered
+    return tile(NT_REG, 2, 2, 2, p.IC % 32 == 0 && p.Ng % 128 == 0 ? 2 : 1, 2, 32);
+
+  if (mode == MODE_FWD && halo3d_eligible(p)) {  // the three-patch form, 8 waves
+    if (p.Ng == 64) return tile(NT_HALO3D, 8, 1, 1, 2, 3, 488, 4);                  // 256 x 64 on waves of 32 x 64
+    if (!halo256_short(p)) return tile(NT_HALO3D, 4, 2, 2, 2, 2, kHaloPR, 4);       // W <= 79: 2 weight stages
+    if (tps2 && halo_tps2_shape(p, 3)) return tile(NT_HALO3D, 4, 2, 2, 2, 2, 336, 7);  // two taps per barrier
+    return tile(NT_HALO3D, 4, 2, 2, 2, 3, 336, 4);                                  // 256 x 128, W <= 39
   }
-  if (CVEC == 8 && ws != nullptr && p.IT == 1 && p.OT == 1 && p.KT == 1) {
+  if (c64_eligible(p)) return tile(NT_C64, c64w, 1, 0, 0, 0, c64::PRMAX);
+  if (!bias && ws != nullptr && !vid) {
     const int ks = halo_splitk(p);
     const long long tiles = (long long)((p.M + 127) / 128) * (p.Ng / 128);
     // the plan is re-made at every call from the current knobs: a workspace sized for another plan
     // (the knobs changed after it was allocated) runs the shape without split-K rather than overrun it
-    if (ks > 1 && tiles * ks * 128 * 128 <= ws->part_floats && tiles <= ws->counters) {
-      launch_halo128<MODE>(p, st, ks, ws->part, ws->cnt);
-      return;
-    }
+    if (ks > 1 && tiles * ks * 128 * 128 <= ws->part_floats && tiles <= ws->counters)
+      return tile(NT_HALO, 2, 2, 2, 2, ring(nst128), 168, 0, ks);
   }
-  if (CVEC == 8 && conv_variant() == 1 && p.IT == 1 && p.OT == 1 && p.KT == 1 && g_nt128_config < 0 && (g_nt64_config < 0 || g_nt64_config == 1) &&
-      p.bx == nullptr && use_small_tile(p, p.Ng % 128 == 0 ? 128 : 64)) {
-    if (p.Ng % 128 == 0) {
-      if (halo_eligible(p) && 64 + 2 * p.OW + 2 <= 104) {  // 64 x 128 halo tile
-        switch (halo_small_nst()) {
-          case 3: launch_halo<MODE, 2, 2, 1, 2, 3, 104>(p, st); break;
-          case 4: launch_halo<MODE, 2, 2, 1, 2, 4, 104>(p, st); break;
-          case 5: launch_halo<MODE, 2, 2, 1, 2, 5, 104>(p, st); break;
-          default: launch_halo<MODE, 2, 2, 1, 2, 2, 104>(p, st); break;
-        }
-      }
-      else
-        launch_glds<MODE, 2, 2, 1, 2, 3>(p, st);  // 64 x 128, k32, 3 stages
-    } else {
-      launch_glds<MODE, 2, 2, 1, 1, 3>(p, st);  // 64 x 64, k32, 3 stages
-    }
-    return;
+  // (the tile overrides switch the 64-row tiles off under either epilogue: the live knobs, not the canonical ones)
+  if (!vid && g_nt128_config < 0 && (g_nt64_config < 0 || g_nt64_config == 1) && p.bx == nullptr &&
+      use_small_tile(p, p.Ng % 128 == 0 ? 128 : 64)) {
+    if (p.Ng % 128 != 0) return tile(NT_GATHER, 2, 2, 1, 1, 3, 32);  // 64 x 64, k32, 3 stages
+    if (halo_eligible(p) && 64 + 2 * p.OW + 2 <= 104) return tile(NT_HALO, 2, 2, 1, 2, ring(nst64), 104);  // 64 x 128
+    return tile(NT_GATHER, 2, 2, 1, 2, 3, 32);  // 64 x 128, k32, 3 stages
   }
-  if (CVEC == 8 && conv_variant() == 1 && halo_eligible(p)) {
+  if (halo_eligible(p)) {
     // measured (tools/conv_bench.py): the 4-wave 128 x 128 form at 2 blocks per CU beats the tap
     // gather on layer3/4 (W <= 19: +2..16 %); the 8-wave 256-row forms a patch of the wider layer1/2
     // images needs (1 block per CU) lose to it (-1..-20 %), so those keep the tap-gather kernel
-    if (p.Ng % 128 == 0 && (g_halo == 2 || 128 + 2 * p.OW + 2 > 168 || halo8_pick(p))) {
-      if (256 + 2 * p.OW + 2 <= 336) {
-        if (halo8_form() == 1)
-          launch_halo<MODE, 2, 2, 4, 2, 3, 336>(p, st);  // same tile on 4 waves of 128 x 64 (0.75 KB LDS per MFMA)
-        else if (halo8_nst() == 4)
-          launch_halo<MODE, 4, 2, 2, 2, 4, 336>(p, st);  // 4-stage weight ring: 150 KB of LDS, still 1 block/CU
-        else if (halo_tps2(p))
-          launch_halo<MODE, 4, 2, 2, 2, 2, 336, 3>(p, st);  // ... two taps per barrier (layer4)
-        else
-          launch_halo<MODE, 4, 2, 2, 2, 3, 336>(p, st);  // 256 x 128, 8 waves, W <= 39 (layer2)
-      }
-      else
-        launch_halo<MODE, 4, 2, 2, 2, 2>(p, st);  // W <= 79: 2 weight stages to fit the 416-row patches
+    if (p.Ng % 128 == 0 && (g_halo == 2 || !halo128_fits(p) || halo8_pick(p))) {
+      if (!halo256_short(p)) return tile(NT_HALO, 4, 2, 2, 2, 2, kHaloPR);  // W <= 79: 2 weight stages fit 416 rows
+      if (form8 == 1) return tile(NT_HALO, 2, 2, 4, 2, 3, 336);  // same tile on 4 waves of 128 x 64
+      if (nst8 == 4) return tile(NT_HALO, 4, 2, 2, 2, 4, 336);   // 4-stage weight ring: 150 KB of LDS, 1 block/CU
+      if (tps2 && halo_tps2_shape(p)) return tile(NT_HALO, 4, 2, 2, 2, 2, 336, 3);  // two taps per barrier (layer4)
+      return tile(NT_HALO, 4, 2, 2, 2, 3, 336);                  // 256 x 128, 8 waves, W <= 39 (layer2)
     }
-    else if (g_halo == 2)
-      launch_halo<MODE, 4, 2, 2, 1>(p, st);  // 256 x 64, 8 waves (A/B only)
-    else
-      launch_halo128<MODE>(p, st);  // 128 x 128, 4 waves
-    return;
+    if (g_halo == 2) return tile(NT_HALO, 4, 2, 2, 1, 3, kHaloPR);  // 256 x 64, 8 waves (A/B only)
+    // the 4-wave 128 x 128 tile by weight-ring depth (avt_set_halo_stages / AVT_HALO_NST): 2 stages (80 KB LDS, 2
+    // blocks per CU; one 16 KiB weight stage in flight behind each step's 16 MFMAs per wave) or 3-5 (96-128 KB, 1
+    // block per CU; NSTB-1 stages in flight)
+    return tile(NT_HALO, 2, 2, 2, 2, ring(nst128), 168);
   }
-  if (CVEC == 8 && conv_variant() == 1) {
-    if (p.Ng % 128 == 0) {
-      // default: 256-row tiles (8 waves) where the GEMM is tall enough to fill the chip with them
-      // (layer2, the stride-2 convs), 128 x 128 k64 tiles for the short layer3/4 GEMMs
-      // Conv3d (27 taps: 3x the K of a 3x3) keeps the 128 x 128 k64 tile unless K is short: on the R3D-18
-      // trunk (tools/conv3d_bench.py, profiles/r5_conv3d_tiles.txt) it is 10-15 % faster than the 256-row
-      // form on layer2/3's 3x3x3 convs; at layer2.0's K = 1728 the two are within 3 %
-      const bool vid = p.IT > 1 || p.OT > 1 || p.KT > 1;
-      const int cfg = g_nt128_config >= 0 ? g_nt128_config : (p.M >= 65536 && (!vid || p.Kg < 3072) ? 6 : 1);
-      switch (cfg) {
-        case 1: launch_glds<MODE, 2, 2, 2, 2, 2, 64>(p, st); break;  // 128 x 128, k64, 2 stages
-        case 2: launch_glds<MODE, 2, 2, 2, 2, 3, 64>(p, st); break;  // 128 x 128, k64, 3 stages
-        case 3: launch_glds<MODE, 2, 2, 4, 2, 3>(p, st); break;      // 256 x 128, k32, 3 stages
-        case 4: launch_glds<MODE, 2, 2, 4, 2, 2, 64>(p, st); break;  // 256 x 128, k64, 2 stages
-        case 5: launch_glds<MODE, 4, 2, 2, 2, 2, 64>(p, st); break;  // 256 x 128, 8 waves, k64, 2 stages
-        case 6: launch_glds<MODE, 4, 2, 2, 2, 3>(p, st); break;      // 256 x 128, 8 waves, k32, 3 stages
-        default: launch_glds<MODE, 2, 2, 2, 2>(p, st); break;        // 128 x 128, k32, 4 stages
-      }
-    } else {  // 64-wide N (layer1 / stem-fed convs)
-      // auto (-1): 1, or 2 (4 stages) for a Conv3d -- R3D-18 layer1, profiles/r5_conv3d_tiles.txt: 548-579 us
-      // against 557-683 us per conv, ahead in every ordering measured
-      switch (g_nt64_config >= 0 ? g_nt64_config : (p.IT > 1 || p.OT > 1 || p.KT > 1 ? 2 : 1)) {
-        case 0: launch_glds<MODE, 4, 1, 2, 2, 4>(p, st); break;  // 256 x 64, 4 stages
-        case 2: launch_glds<MODE, 2, 2, 2, 1, 4>(p, st); break;  // 128 x 64, 4 stages
-        case 3: launch_glds<MODE, 4, 1, 2, 2, 2>(p, st); break;  // 256 x 64, 2 stages
-        case 4: launch_glds<MODE, 2, 2, 2, 1, 3, 64>(p, st); break;  // 128 x 64, k64, 3 stages
-        case 5: launch_glds<MODE, 4, 1, 2, 2, 2, 64>(p, st); break;  // 256 x 64, k64, 2 stages
-        case 6: launch_glds<MODE, 2, 2, 2, 1, 2, 64>(p, st); break;  // 128 x 64, k64, 2 stages
-        case 7: launch_glds<MODE, 4, 2, 2, 1, 3, 64>(p, st); break;  // 256 x 64, 8 waves, k64, 3 stages
-        case 8: launch_glds<MODE, 4, 2, 2, 1, 2, 64>(p, st); break;  // 256 x 64, 8 waves, k64, 2 stages
-        default: launch_glds<MODE, 2, 2, 2, 1, 3>(p, st); break;  // 128 x 64, 3 stages
-      }
+  NtPlan g;
+  if (p.Ng % 128 == 0) {
+    // default: 256-row tiles (8 waves) where the GEMM is tall enough to fill the chip with them
+    // (layer2, the stride-2 convs), 128 x 128 k64 tiles for the short layer3/4 GEMMs
+    // Conv3d (27 taps: 3x the K of a 3x3) keeps the 128 x 128 k64 tile unless K is short: on the R3D-18
+    // trunk (tools/conv3d_bench.py, profiles/r5_conv3d_tiles.txt) it is 10-15 % faster than the 256-row
+    // form on layer2/3's 3x3x3 convs; at layer2.0's K = 1728 the two are within 3 %
+    switch (cfg128 >= 0 ? cfg128 : (p.M >= 65536 && (!vid || p.Kg < 3072) ? 6 : 1)) {
+      case 1: g = tile(NT_GATHER, 2, 2, 2, 2, 2, 64); break;   // 128 x 128, k64, 2 stages
+      case 2: g = tile(NT_GATHER, 2, 2, 2, 2, 3, 64); break;   // 128 x 128, k64, 3 stages
+      case 3: g = tile(NT_GATHER, 2, 2, 4, 2, 3, 32); break;   // 256 x 128, k32, 3 stages
+      case 4: g = tile(NT_GATHER, 2, 2, 4, 2, 2, 64); break;   // 256 x 128, k64, 2 stages
+      case 5: g = tile(NT_GATHER, 4, 2, 2, 2, 2, 64); break;   // 256 x 128, 8 waves, k64, 2 stages
+      case 6: g = tile(NT_GATHER, 4, 2, 2, 2, 3, 32); break;   // 256 x 128, 8 waves, k32, 3 stages
+      default: g = tile(NT_GATHER, 2, 2, 2, 2, 4, 32); break;  // 128 x 128, k32, 4 stages
     }
-    return;
+  } else {  // 64-wide N (layer1 / stem-fed convs)
+    // auto (-1): 1, or 2 (4 stages) for a Conv3d -- R3D-18 layer1, profiles/r5_conv3d_tiles.txt: 548-579 us
+    // against 557-683 us per conv, ahead in every ordering measured
+    switch (cfg64 >= 0 ? cfg64 : (vid ? 2 : 1)) {
+      case 0: g = tile(NT_GATHER, 4, 1, 2, 2, 4, 32); break;   // 256 x 64, 4 stages
+      case 2: g = tile(NT_GATHER, 2, 2, 2, 1, 4, 32); break;   // 128 x 64, 4 stages
+      case 3: g = tile(NT_GATHER, 4, 1, 2, 2, 2, 32); break;   // 256 x 64, 2 stages
+      case 4: g = tile(NT_GATHER, 2, 2, 2, 1, 3, 64); break;   // 128 x 64, k64, 3 stages
+      case 5: g = tile(NT_GATHER, 4, 1, 2, 2, 2, 64); break;   // 256 x 64, k64, 2 stages
+      case 6: g = tile(NT_GATHER, 2, 2, 2, 1, 2, 64); break;   // 128 x 64, k64, 2 stages
+      case 7: g = tile(NT_GATHER, 4, 2, 2, 1, 3, 64); break;   // 256 x 64, 8 waves, k64, 3 stages
+      case 8: g = tile(NT_GATHER, 4, 2, 2, 1, 2, 64); break;   // 256 x 64, 8 waves, k64, 2 stages
+      default: g = tile(NT_GATHER, 2, 2, 2, 1, 3, 32); break;  // 128 x 64, 3 stages
+    }
   }
-  const int grid = ((p.M + BM - 1) / BM) * (p.Ng / BN);
-  hipLaunchKernelGGL((gemm_nt_kernel<MODE, CVEC, BM, BN>), dim3(grid), dim3(256), 0, st, p);
+  // a 64-deep k-tile needs whole 64-channel taps: else the 4-wave k32 tile of the same width
+  if (g.kp == 64 && p.IC % 64 != 0) g = tile(NT_GATHER, 2, 2, 2, g.wn * g.tn / 2, 3, 32);
+  return g;
 }
 
+// Launches a plan.  Every launch_halo / launch_glds instantiation is named here, once; the bias epilogues (EPI) are
+// instantiated for the tiles plan_nt can give them -- its canonical ones -- and the rest only for the plain epilogue.
+// False: no such instantiation (a planner bug).
+template <int MODE, int EPI = EPI_PLAIN>
+static bool launch_plan(const NtPlan& pl, const GemmNTParams& p, hipStream_t st, const SplitWs* ws = nullptr) {
+  constexpr bool PLAIN = EPI == EPI_PLAIN;
+  float* part = pl.ksplit > 1 ? ws->part : nullptr;
+  int* cnt = pl.ksplit > 1 ? ws->cnt : nullptr;
+  const auto is = [&pl](int wm, int wn, int tm, int tn, int nst, int kp, int opt = 0) {
+    return pl.wm == wm && pl.wn == wn && pl.tm == tm && pl.tn == tn && pl.nst == nst && pl.kp == kp && pl.opt == opt;
+  };
+#define AVT_HALO(WM, WN, TM, TN, NST, PR, OPT)                                              \
+  if (is(WM, WN, TM, TN, NST, PR, OPT)) {                                                   \
+    launch_halo<MODE, WM, WN, TM, TN, NST, PR, OPT, !PLAIN>(p, st, pl.ksplit, part, cnt);   \
+    return true;                                                                            \
+  }
+#define AVT_GLDS(WM, WN, TM, TN, NST, BK)                     \
+  if (is(WM, WN, TM, TN, NST, BK)) {                          \
+    launch_glds<MODE, WM, WN, TM, TN, NST, BK, EPI>(p, st);   \
+    return true;                                              \
+  }
+  switch (pl.family) {
+    case NT_C64:
+      if constexpr (EPI != EPI_BIAS3D) {
+        launch_c64<MODE, !PLAIN>(p, st, pl.wm);
+        return true;
+      }
+      break;
+    case NT_HALO:
+      if constexpr (EPI != EPI_BIAS3D) {
+        AVT_HALO(2, 2, 1, 2, 3, 104, 0)      // 64 x 128
+        AVT_HALO(2, 2, 2, 2, 2, 168, 0)      // 128 x 128
+        AVT_HALO(4, 2, 2, 2, 3, 336, 0)      // 256 x 128, W <= 39
+        AVT_HALO(4, 2, 2, 2, 2, kHaloPR, 0)  // 256 x 128, W <= 79
+        AVT_HALO(4, 2, 2, 1, 3, kHaloPR, 0)  // 256 x 64
+      }
+      if constexpr (PLAIN) {  // avt_set_halo_stages, avt_set_halo8_form / _nst, avt_set_halo_tps2
+        AVT_HALO(2, 2, 1, 2, 2, 104, 0)
+        AVT_HALO(2, 2, 1, 2, 4, 104, 0)
+        AVT_HALO(2, 2, 1, 2, 5, 104, 0)
+        AVT_HALO(2, 2, 2, 2, 3, 168, 0)
+        AVT_HALO(2, 2, 2, 2, 4, 168, 0)
+        AVT_HALO(2, 2, 2, 2, 5, 168, 0)
+        AVT_HALO(2, 2, 4, 2, 3, 336, 0)
+        AVT_HALO(4, 2, 2, 2, 4, 336, 0)
+        AVT_HALO(4, 2, 2, 2, 2, 336, 3)
+      }
+      break;
+    case NT_HALO3D:  // OPT 4: the Conv3d 3x3x3 / stride 1 / pad 1 form (conv_halo.h; forward only)
+      if constexpr (MODE == MODE_FWD && EPI != EPI_BIAS2D) {
+        AVT_HALO(8, 1, 1, 2, 3, 488, 4)
+        AVT_HALO(4, 2, 2, 2, 3, 336, 4)
+        AVT_HALO(4, 2, 2, 2, 2, kHaloPR, 4)
+        if constexpr (PLAIN) AVT_HALO(4, 2, 2, 2, 2, 336, 7)  // avt_set_halo_tps2
+      }
+      break;
+    case NT_GATHER:
+      AVT_GLDS(2, 2, 1, 1, 3, 32)
+      AVT_GLDS(2, 2, 1, 2, 3, 32)
+      AVT_GLDS(2, 2, 2, 1, 3, 32)
+      AVT_GLDS(2, 2, 2, 2, 2, 64)
+      AVT_GLDS(2, 2, 2, 2, 3, 32)
+      AVT_GLDS(4, 2, 2, 2, 3, 32)
+      if constexpr (EPI != EPI_BIAS2D) AVT_GLDS(2, 2, 2, 1, 4, 32)  // a Conv3d's 64-wide tile
+      if constexpr (PLAIN) {  // avt_set_nt128_config, avt_set_nt64_config
+        AVT_GLDS(2, 2, 2, 2, 4, 32)
+        AVT_GLDS(2, 2, 2, 2, 3, 64)
+        AVT_GLDS(2, 2, 4, 2, 3, 32)
+        AVT_GLDS(2, 2, 4, 2, 2, 64)
+        AVT_GLDS(4, 2, 2, 2, 2, 64)
+        AVT_GLDS(4, 1, 2, 2, 4, 32)
+        AVT_GLDS(4, 1, 2, 2, 2, 32)
+        AVT_GLDS(2, 2, 2, 1, 3, 64)
+        AVT_GLDS(4, 1, 2, 2, 2, 64)
+        AVT_GLDS(2, 2, 2, 1, 2, 64)
+        AVT_GLDS(4, 2, 2, 1, 3, 64)
+        AVT_GLDS(4, 2, 2, 1, 2, 64)
+      }
+      break;
+    case NT_REG:
+      if constexpr (PLAIN) {
+        const dim3 grid(((p.M + 127) / 128) * (p.Ng / (64 * pl.tn)));
+        if (p.IC % 32 == 0 && pl.tn == 2)
+          hipLaunchKernelGGL((gemm_nt_kernel<MODE, 8, 128, 128>), grid, dim3(256), 0, st, p);
+        else if (p.IC % 32 == 0)
+          hipLaunchKernelGGL((gemm_nt_kernel<MODE, 8, 128, 64>), grid, dim3(256), 0, st, p);
+        else if constexpr (MODE == MODE_FWD) {  // the stems
+          if (p.IC == 4)
+            hipLaunchKernelGGL((gemm_nt_kernel<MODE, 4, 128, 64>), grid, dim3(256), 0, st, p);
+          else
+            hipLaunchKernelGGL((gemm_nt_kernel<MODE, 1, 128, 64>), grid, dim3(256), 0, st, p);
+        } else {
+          break;
+        }
+        return true;
+      }
+      break;
+  }
+#undef AVT_HALO
+#undef AVT_GLDS
+  return false;
+}
+
+// The forward GemmNTParams of a conv (a 2-D conv: T = KT = 1, pad_t = 0); the caller adds its epilogue operands.
+// False: an activation tensor reaches 2 GiB (the kernels' 32-bit buffer offsets).
+static bool fwd_params(GemmNTParams& p, const void* x, const void* wpack, void* y, int N, int T, int H, int W, int Cp,
+                       int K, int KT, int R, int S, int stride, int pad_t, int pad, int Kg) {
+  p.act = (const bf16_t*)x;
+  p.wmat = (const bf16_t*)wpack;
+  p.out = (bf16_t*)y;
+  p.IT = T; p.IH = H; p.IW = W; p.IC = Cp;
+  p.OT = T + 2 * pad_t - KT + 1;
+  p.OH = conv_out(H, R, stride, pad);
+  p.OW = conv_out(W, S, stride, pad);
+  p.M = N * p.OT * p.OH * p.OW;
+  p.Ng = K;
+  p.Kg = Kg;
+  p.KT = KT; p.R = R; p.S = S; p.stride = stride; p.pad = pad; p.pad_t = pad_t;
+  return (size_t)N * T * H * W * Cp * 2 < (1ull << 31) && (size_t)N * p.OT * p.OH * p.OW * K * 2 < (1ull << 31);
+}
+
+// One of the two bias epilogues' launches (plan_nt resolves which)
+static bool launch_plan_bias(const NtPlan& pl, const GemmNTParams& p, hipStream_t st) {
+  return pl.epi == EPI_BIAS2D ? launch_plan<MODE_FWD, EPI_BIAS2D>(pl, p, st) : launch_plan<MODE_FWD, EPI_BIAS3D>(pl, p, st);
+}
 
 static int conv2d_fwd_impl(const void* x, const void* wpack, void* y, double* bn_acc, int N, int H, int W, int Cp,
                            int K, int R, int S, int stride, int pad, int Kg, const SplitWs* ws, void* stream);
@@ -1261,7 +1346,7 @@ extern "C" int avt_conv2d_splitk_plan(int N, int H, int W, int C, int K, int R, 
   }
   p.M = N * p.OH * p.OW;
   if (p.IC % 64 != 0 || p.Ng % 64 != 0 || p.M <= 0) return AVT_OK;
-  const int ks = halo_splitk(p);
+  const int ks = plan_nt(p, dgrad ? MODE_DGRAD : MODE_FWD, EPI_PLAIN, &kAnySplitWs).ksplit;
   if (ks <= 1) return AVT_OK;
   const int tiles = ((p.M + 127) / 128) * (p.Ng / 128);
   *part_floats = (long long)tiles * ks * 128 * 128;
@@ -1307,25 +1392,12 @@ static int conv2d_fwd_impl(const void* x, const void* wpack, void* y, double* bn
   AVT_REQUIRE(Cp % 32 != 0 || R * S <= kMaxTaps, "conv2d_fwd: at most %d taps for C%%32==0", kMaxTaps);
   AVT_REQUIRE(stride == 1 || stride == 2, "conv2d_fwd: stride must be 1 or 2");
   GemmNTParams p{};
-  p.act = (const bf16_t*)x;
-  p.wmat = (const bf16_t*)wpack;
-  p.out = (bf16_t*)y;
-  p.add = nullptr;
-  p.stats = bn_acc;
-  p.IH = H; p.IW = W; p.IC = Cp;
-  p.OH = conv_out(H, R, stride, pad);
-  p.OW = conv_out(W, S, stride, pad);
-  p.IT = p.OT = p.KT = 1;
-  p.pad_t = 0;
-  p.M = N * p.OH * p.OW;
-  AVT_REQUIRE((size_t)N * H * W * Cp * 2 < (1ull << 31) && (size_t)p.M * K * 2 < (1ull << 31),
+  AVT_REQUIRE(fwd_params(p, x, wpack, y, N, 1, H, W, Cp, K, 1, R, S, stride, 0, pad, Kg),
               "conv2d_fwd: activation tensors must stay below 2 GiB (32-bit buffer offsets)");
-  p.Ng = K;
-  p.Kg = Kg;
-  p.R = R; p.S = S; p.stride = stride; p.pad = pad;
+  p.stats = bn_acc;
   hipStream_t st = (hipStream_t)stream;
-  if ((Cp == 4 || Cp == 1) && stem_enabled() && K == 64 && R == 7 && S == 7 && stride == 2 && pad == 3 &&
-      (Cp == 4 ? stem_fits<4>(p.OW) : stem_fits<1>(p.OW))) {
+  const NtPlan pl = plan_nt(p, MODE_FWD, EPI_PLAIN, ws);
+  if (pl.family == NT_STEM) {
     StemArgs sa{};
     sa.x = p.act;
     sa.w = p.wmat;
@@ -1346,60 +1418,8 @@ static int conv2d_fwd_impl(const void* x, const void* wpack, void* y, double* bn
       hipLaunchKernelGGL(conv_stem_fwd_kernel<1>, dim3(grid), dim3(kStemNW * 64), lds, st, sa);
     return check_launch("conv2d_fwd (stem)");
   }
-  const bool bn128 = (K % 128 == 0);
-  if (Cp == 4) {
-    launch_nt<MODE_FWD, 4, 128, 64>(p, st);
-  } else if (Cp == 1) {
-    launch_nt<MODE_FWD, 1, 128, 64>(p, st);
-  } else if (bn128) {
-    launch_nt<MODE_FWD, 8, 128, 128>(p, st, ws);
-  } else {
-    launch_nt<MODE_FWD, 8, 128, 64>(p, st);
-  }
+  AVT_REQUIRE(launch_plan<MODE_FWD>(pl, p, st, ws), "conv2d_fwd: no kernel for the plan");
   return check_launch("conv2d_fwd");
-}
-
-// The planner of avt_conv2d_fwd_bias: launch_nt's choice of kernel family and tile for the shape under the same
-// planner knobs (c64 / halo 64-row, 4-wave, 8-wave / tap gather and its tiles by GEMM size), so a shape runs the
-// bias epilogue on the main loop its plain forward runs.  The knobs that only trade ring depth or wave layout
-// (halo stages, halo8 form / nst / tps2, AVT_C64_WAVES, the nt64 / nt128 tile overrides) stay at their defaults here:
-// they do not change a result bit, and each would cost another instantiation.  No split-K.
-static void launch_nt_bias(const GemmNTParams& p, hipStream_t st) {
-  if (c64_eligible(p)) {
-    launch_c64<MODE_FWD, true>(p, st);
-    return;
-  }
-  if (g_nt128_config < 0 && (g_nt64_config < 0 || g_nt64_config == 1) &&
-      use_small_tile(p, p.Ng % 128 == 0 ? 128 : 64)) {
-    if (p.Ng % 128 != 0)
-      launch_glds_bias<2, 2, 1, 1, 3>(p, st);  // 64 x 64, k32, 3 stages
-    else if (halo_eligible(p) && 64 + 2 * p.OW + 2 <= 104)
-      launch_halo<MODE_FWD, 2, 2, 1, 2, 3, 104, 0, true>(p, st);  // 64 x 128 halo tile
-    else
-      launch_glds_bias<2, 2, 1, 2, 3>(p, st);  // 64 x 128, k32, 3 stages
-    return;
-  }
-  if (halo_eligible(p)) {
-    if (p.Ng % 128 == 0 && (g_halo == 2 || 128 + 2 * p.OW + 2 > 168 || halo8_pick(p))) {
-      if (256 + 2 * p.OW + 2 <= 336)
-        launch_halo<MODE_FWD, 4, 2, 2, 2, 3, 336, 0, true>(p, st);  // 256 x 128, 8 waves, W <= 39
-      else
-        launch_halo<MODE_FWD, 4, 2, 2, 2, 2, kHaloPR, 0, true>(p, st);  // W <= 79
-    } else if (g_halo == 2) {
-      launch_halo<MODE_FWD, 4, 2, 2, 1, 3, kHaloPR, 0, true>(p, st);  // 256 x 64, 8 waves (A/B only)
-    } else {
-      launch_halo<MODE_FWD, 2, 2, 2, 2, 2, 168, 0, true>(p, st);  // 128 x 128, 4 waves
-    }
-    return;
-  }
-  if (p.Ng % 128 == 0) {
-    if (p.M >= 65536)
-      launch_glds_bias<4, 2, 2, 2, 3>(p, st);  // 256 x 128, 8 waves, k32, 3 stages
-    else
-      launch_glds_bias<2, 2, 2, 2, 2, 64>(p, st);  // 128 x 128, k64, 2 stages
-  } else {
-    launch_glds_bias<2, 2, 2, 1, 3>(p, st);  // 128 x 64, 3 stages
-  }
 }
 
 // Forward conv with BatchNorm folded in (include/avt.h): y = [relu](conv(x, wpack) + bias[k] (+ residual)).
@@ -1418,23 +1438,13 @@ extern "C" int avt_conv2d_fwd_bias(const void* x, const void* wpack, void* y, in
   AVT_REQUIRE(pad >= 0 && H + 2 * pad >= R && W + 2 * pad >= S, "conv2d_fwd_bias: empty output");
   AVT_REQUIRE(conv_variant() == 1, "conv2d_fwd_bias: needs the LDS-DMA conv kernels (AVT_CONV_VARIANT=1)");
   GemmNTParams p{};
-  p.act = (const bf16_t*)x;
-  p.wmat = (const bf16_t*)wpack;
-  p.out = (bf16_t*)y;
+  AVT_REQUIRE(fwd_params(p, x, wpack, y, N, 1, H, W, Cp, K, 1, R, S, stride, 0, pad, Kg),
+              "conv2d_fwd_bias: activation tensors must stay below 2 GiB (32-bit buffer offsets)");
   p.add = (const bf16_t*)residual;
   p.bias = bias;
   p.relu = relu ? 1 : 0;
-  p.IH = H; p.IW = W; p.IC = Cp;
-  p.OH = conv_out(H, R, stride, pad);
-  p.OW = conv_out(W, S, stride, pad);
-  p.IT = p.OT = p.KT = 1;
-  p.M = N * p.OH * p.OW;
-  AVT_REQUIRE((size_t)N * H * W * Cp * 2 < (1ull << 31) && (size_t)p.M * K * 2 < (1ull << 31),
-              "conv2d_fwd_bias: activation tensors must stay below 2 GiB (32-bit buffer offsets)");
-  p.Ng = K;
-  p.Kg = Kg;
-  p.R = R; p.S = S; p.stride = stride; p.pad = pad;
-  launch_nt_bias(p, (hipStream_t)stream);
+  AVT_REQUIRE(launch_plan_bias(plan_nt(p, MODE_FWD, EPI_BIAS2D, nullptr), p, (hipStream_t)stream),
+              "conv2d_fwd_bias: no kernel for the plan");
   return check_launch("conv2d_fwd_bias");
 }
 
@@ -1482,11 +1492,8 @@ static int conv2d_dgrad_impl(const void* dy, const void* wt, void* dx, const voi
     p.bskip00 = epi->skip_class00;
     p.bappend = epi->append_slots ? 1 : 0;
   }
-  hipStream_t st = (hipStream_t)stream;
-  if (C % 128 == 0)
-    launch_nt<MODE_DGRAD, 8, 128, 128>(p, st, ws);
-  else
-    launch_nt<MODE_DGRAD, 8, 128, 64>(p, st);
+  AVT_REQUIRE(launch_plan<MODE_DGRAD>(plan_nt(p, MODE_DGRAD, EPI_PLAIN, ws), p, (hipStream_t)stream, ws),
+              "conv2d_dgrad: no kernel for the plan");
   return check_launch("conv2d_dgrad");
 }
 
@@ -1535,66 +1542,20 @@ static int conv3d_fwd_impl(const void* x, const void* wpack, void* y, double* bn
   AVT_REQUIRE(KT * R * S <= kMaxTaps && KT >= 1 && R >= 1 && S >= 1, "conv3d_fwd: at most %d taps", kMaxTaps);
   AVT_REQUIRE(stride == 1 || stride == 2, "conv3d_fwd: spatial stride must be 1 or 2");
   GemmNTParams p{};
-  p.act = (const bf16_t*)x;
-  p.wmat = (const bf16_t*)wpack;
-  p.out = (bf16_t*)y;
+  const bool fits = fwd_params(p, x, wpack, y, N, T, H, W, Cp, K, KT, R, S, stride, pad_t, pad, KT * R * S * Cp);
+  AVT_REQUIRE(p.OT >= 1 && p.OH >= 1 && p.OW >= 1, "conv3d_fwd: empty output");
+  AVT_REQUIRE(fits, "conv3d_fwd: activation tensors must stay below 2 GiB (32-bit buffer offsets)");
+  AVT_REQUIRE(conv_variant() == 1, "conv3d_fwd: needs the LDS-DMA conv kernels (AVT_CONV_VARIANT=1)");
   p.add = (const bf16_t*)add;
   p.stats = bn_acc;
-  p.IT = T; p.IH = H; p.IW = W; p.IC = Cp;
-  p.OT = T + 2 * pad_t - KT + 1;
-  p.OH = conv_out(H, R, stride, pad);
-  p.OW = conv_out(W, S, stride, pad);
-  AVT_REQUIRE(p.OT >= 1 && p.OH >= 1 && p.OW >= 1, "conv3d_fwd: empty output");
-  p.M = N * p.OT * p.OH * p.OW;
-  p.Ng = K;
-  p.Kg = KT * R * S * Cp;
-  p.KT = KT; p.R = R; p.S = S; p.stride = stride; p.pad = pad; p.pad_t = pad_t;
-  AVT_REQUIRE((size_t)N * T * H * W * Cp * 2 < (1ull << 31) && (size_t)p.M * K * 2 < (1ull << 31),
-              "conv3d_fwd: activation tensors must stay below 2 GiB (32-bit buffer offsets)");
-  AVT_REQUIRE(conv_variant() == 1, "conv3d_fwd: needs the LDS-DMA conv kernels (AVT_CONV_VARIANT=1)");
-  hipStream_t st = (hipStream_t)stream;
-  if (halo3d_launch<>(p, st)) return check_launch("conv3d_fwd");
-  if (K % 128 == 0)
-    launch_nt<MODE_FWD, 8, 128, 128>(p, st);
-  else
-    launch_nt<MODE_FWD, 8, 128, 64>(p, st);
+  AVT_REQUIRE(launch_plan<MODE_FWD>(plan_nt(p, MODE_FWD, EPI_PLAIN, nullptr), p, (hipStream_t)stream),
+              "conv3d_fwd: no kernel for the plan");
   return check_launch("conv3d_fwd");
 }
 
 extern "C" int avt_conv3d_fwd(const void* x, const void* wpack, void* y, double* bn_acc, int N, int T, int H, int W,
                               int Cp, int K, int KT, int R, int S, int stride, int pad_t, int pad, void* stream) {
   return conv3d_fwd_impl(x, wpack, y, bn_acc, nullptr, N, T, H, W, Cp, K, KT, R, S, stride, pad_t, pad, stream);
-}
-
-// The planner of avt_conv3d_fwd_bias: conv3d_fwd_impl's choice for the shape under the same knobs -- the halo kernel's
-// three-patch form where halo3d_launch takes it, else launch_nt's tap-gather tile for a Conv3d (or, T = KT = 1: for the
-// 2-D conv of that tap count, the 49-tap folded video stem) -- so a shape keeps the main loop its plain forward runs.
-// As launch_nt_bias, the nt64 / nt128 tile overrides stay at their defaults.
-static void launch_nt3d_bias(const GemmNTParams& p, hipStream_t st) {
-  if (halo3d_launch<true>(p, st)) return;
-  const bool vid = p.IT > 1 || p.OT > 1 || p.KT > 1;
-  if (!vid && p.R * p.S <= 9) {  // a 2-D conv avt_conv2d_fwd_bias takes: its planner
-    launch_nt_bias(p, st);
-    return;
-  }
-  if (!vid && g_nt128_config < 0 && (g_nt64_config < 0 || g_nt64_config == 1) &&
-      use_small_tile(p, p.Ng % 128 == 0 ? 128 : 64)) {
-    if (p.Ng % 128 != 0)
-      launch_glds3d_bias<2, 2, 1, 1, 3>(p, st);  // 64 x 64, k32, 3 stages
-    else
-      launch_glds3d_bias<2, 2, 1, 2, 3>(p, st);  // 64 x 128, k32, 3 stages
-    return;
-  }
-  if (p.Ng % 128 == 0) {
-    if (p.M >= 65536 && (!vid || p.Kg < 3072))
-      launch_glds3d_bias<4, 2, 2, 2, 3>(p, st);  // 256 x 128, 8 waves, k32, 3 stages
-    else
-      launch_glds3d_bias<2, 2, 2, 2, 2, 64>(p, st);  // 128 x 128, k64, 2 stages
-  } else if (vid) {
-    launch_glds3d_bias<2, 2, 2, 1, 4>(p, st);  // 128 x 64, 4 stages
-  } else {
-    launch_glds3d_bias<2, 2, 2, 1, 3>(p, st);  // 128 x 64, 3 stages
-  }
 }
 
 // Conv3d forward with BatchNorm folded in (include/avt.h): y = [relu](conv3d(x, wpack) + bias[k] (+ residual)).
@@ -1612,25 +1573,40 @@ extern "C" int avt_conv3d_fwd_bias(const void* x, const void* wpack, void* y, in
   AVT_REQUIRE(pad_t >= 0 && pad >= 0, "conv3d_fwd_bias: negative padding");
   AVT_REQUIRE(conv_variant() == 1, "conv3d_fwd_bias: needs the LDS-DMA conv kernels (AVT_CONV_VARIANT=1)");
   GemmNTParams p{};
-  p.act = (const bf16_t*)x;
-  p.wmat = (const bf16_t*)wpack;
-  p.out = (bf16_t*)y;
+  const bool fits = fwd_params(p, x, wpack, y, N, T, H, W, Cp, K, KT, R, S, stride, pad_t, pad, KT * R * S * Cp);
+  AVT_REQUIRE(p.OT >= 1 && H + 2 * pad >= R && W + 2 * pad >= S, "conv3d_fwd_bias: empty output");
+  AVT_REQUIRE(fits, "conv3d_fwd_bias: activation tensors must stay below 2 GiB (32-bit buffer offsets)");
   p.add = (const bf16_t*)residual;
   p.bias = bias;
   p.relu = relu ? 1 : 0;
-  p.IT = T; p.IH = H; p.IW = W; p.IC = Cp;
-  p.OT = T + 2 * pad_t - KT + 1;
-  p.OH = conv_out(H, R, stride, pad);
-  p.OW = conv_out(W, S, stride, pad);
-  AVT_REQUIRE(p.OT >= 1 && H + 2 * pad >= R && W + 2 * pad >= S, "conv3d_fwd_bias: empty output");
-  AVT_REQUIRE((size_t)N * T * H * W * Cp * 2 < (1ull << 31) && (size_t)N * p.OT * p.OH * p.OW * K * 2 < (1ull << 31),
-              "conv3d_fwd_bias: activation tensors must stay below 2 GiB (32-bit buffer offsets)");
-  p.M = N * p.OT * p.OH * p.OW;
-  p.Ng = K;
-  p.Kg = KT * R * S * Cp;
-  p.KT = KT; p.R = R; p.S = S; p.stride = stride; p.pad = pad; p.pad_t = pad_t;
-  launch_nt3d_bias(p, (hipStream_t)stream);
+  AVT_REQUIRE(launch_plan_bias(plan_nt(p, MODE_FWD, EPI_BIAS3D, nullptr), p, (hipStream_t)stream),
+              "conv3d_fwd_bias: no kernel for the plan");
   return check_launch("conv3d_fwd_bias");
+}
+
+// The plan of a forward call, from its shape and the current knobs alone (include/avt_tuning.h): no GPU, no launch.
+extern "C" int avt_conv_fwd_plan(int N, int T, int H, int W, int Cp, int K, int KT, int R, int S, int stride, int pad_t,
+                                 int pad, int epi, int* plan) {
+  AVT_REQUIRE(plan, "conv_fwd_plan: null pointer");
+  AVT_REQUIRE(epi >= 0 && epi <= 3, "conv_fwd_plan: epi=%d (0 plain, 1 / 2 the 2-D / 3-D bias entry, 3 plain with a workspace)", epi);
+  const bool bias = epi == EPI_BIAS2D || epi == EPI_BIAS3D;
+  AVT_REQUIRE(N >= 1 && T >= 1 && H >= 1 && W >= 1 && KT >= 1 && R >= 1 && S >= 1 && pad_t >= 0 && pad >= 0,
+              "conv_fwd_plan: empty input or taps, or negative padding");
+  AVT_REQUIRE(K >= 64 && K % 64 == 0, "conv_fwd_plan: K=%d must be a multiple of 64", K);
+  AVT_REQUIRE((Cp >= 32 && Cp % 32 == 0) || (!bias && T == 1 && KT == 1 && (Cp == 4 || Cp == 1)),
+              "conv_fwd_plan: C=%d unsupported (need %%32, or a plain 2-D stem's 1/4)", Cp);
+  AVT_REQUIRE(KT * R * S <= kMaxTaps || Cp % 32 != 0, "conv_fwd_plan: at most %d taps", kMaxTaps);
+  AVT_REQUIRE(stride == 1 || stride == 2, "conv_fwd_plan: stride must be 1 or 2");
+  AVT_REQUIRE(!bias || conv_variant() == 1, "conv_fwd_plan: the bias epilogues need the LDS-DMA conv kernels");
+  GemmNTParams p{};
+  const bool fits = fwd_params(p, nullptr, nullptr, nullptr, N, T, H, W, Cp, K, KT, R, S, stride, pad_t, pad,
+                               (KT * R * S * Cp + 31) / 32 * 32);
+  AVT_REQUIRE(p.OT >= 1 && p.OH >= 1 && p.OW >= 1, "conv_fwd_plan: empty output");
+  AVT_REQUIRE(fits, "conv_fwd_plan: activation tensors must stay below 2 GiB (32-bit buffer offsets)");
+  const NtPlan pl = plan_nt(p, MODE_FWD, epi == 3 ? EPI_PLAIN : epi, epi == 3 ? &kAnySplitWs : nullptr);
+  const int out[AVT_CONV_PLAN_INTS] = {pl.family, pl.wm, pl.wn, pl.tm, pl.tn, pl.nst, pl.kp, pl.opt, pl.ksplit, pl.epi};
+  for (int i = 0; i < AVT_CONV_PLAN_INTS; ++i) plan[i] = out[i];
+  return AVT_OK;
 }
 
 // One parity class (ph, pw) of a spatially strided Conv3d's input gradient on the tap-gather kernel's Conv3d form:

@@ -107,6 +107,25 @@ int avt_set_wgrad_nst(int nst, int nst_big);
  * auto).  Workspace sizes follow the plan: query avt_conv2d_wgrad_workspace after changing it. */
 int avt_set_wgrad_slots_pct(int pct);
 
+/* Which kernel a forward conv runs, under the knobs as they stand: a host query (no GPU needed, nothing launched).
+ * The shape arguments are avt_conv3d_fwd_bias's (a 2-D conv: T = KT = 1, pad_t = 0; C = 4 or 1: a stem of
+ * avt_conv2d_fwd); epi: 0 = avt_conv2d_fwd / avt_conv3d_fwd, 1 = avt_conv2d_fwd_bias, 2 = avt_conv3d_fwd_bias,
+ * 3 = avt_conv2d_fwd_ws with the workspace avt_conv2d_splitk_plan sizes.  plan[AVT_CONV_PLAN_INTS] receives
+ *   [0] family: 0 c64 (resident weights), 1 halo, 2 halo, Conv3d three-patch form, 3 tap gather, 4 register-staged
+ *       gemm_nt_kernel, 5 the 7x7 stem kernel
+ *   [1..4] WM, WN, TM, TN: waves per block (rows x columns) and 32 x 32 MFMA tiles per wave -- the block computes
+ *       WM*TM*32 x WN*TN*32 outputs (c64: WM = waves of its 256 x 64 tile; stem: WM = wave tiles per block; TM = TN = 0)
+ *   [5] ring stages   [6] k-tile depth (tap gather, register-staged) or LDS patch rows (halo, c64)
+ *   [7] conv_halo_kernel's OPT   [8] split-K factor
+ *   [9] the epilogue instantiated: 0 plain, 1 bias on the narrow (<= 9 taps, 2-D) argument form, 2 bias on the
+ *       Conv3d / long-tap-list form (a 2-D conv of at most 9 taps gets 1 through either bias entry point)
+ * A bias epilogue runs the tile the plain forward of the shape runs under default knobs: the knobs that only trade
+ * ring depth or wave layout (avt_set_halo_stages, avt_set_halo8_form / _nst, avt_set_halo_tps2, AVT_C64_WAVES,
+ * avt_set_nt64_config / avt_set_nt128_config's tile) do not reach it. */
+#define AVT_CONV_PLAN_INTS 10
+int avt_conv_fwd_plan(int N, int T, int H, int W, int Cp, int K, int KT, int R, int S, int stride, int pad_t, int pad,
+                      int epi, int* plan);
+
 #ifdef __cplusplus
 }
 #endif

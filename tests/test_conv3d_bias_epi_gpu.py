@@ -33,6 +33,9 @@ CASES = [
     ("one_column", 0, (20, 4, 2, 1, 64, 128, 1)),
 ]
 STEM_CASES = [(2, 1, 9, 8), (1, 3, 16, 16)]  # video (b, T, H, W)
+# what a form's name claims of avt_conv_fwd_plan's answer (include/avt_tuning.h): the family (2 the halo kernel's
+# three-patch form, 3 tap gather) and the halo form's patch rows; "one_column" runs whichever avt_set_halo3d leaves
+NAMED = {"halo336": (2, 336), "halo416": (2, 416), "halo488": (2, 488), "gather_s1": (3, None), "gather_s2": (3, None)}
 MODES = ["bias", "bias_relu", "bias_res_relu"]
 
 
@@ -130,6 +133,34 @@ def test_zero_bias_is_the_plain_forward(form, halo3d, shape):
         y = _run(shape, x, wp, torch.zeros_like(bias), None, False)
         y0 = _run(shape, x, wp, None, None, False, plain=True)
     assert torch.equal(y.view(torch.int16), y0.view(torch.int16))
+
+
+@pytest.mark.parametrize("form,halo3d,shape", CASES)
+def test_case_runs_the_form_it_names(form, halo3d, shape):
+    """The planner's own account of the call (avt_conv_fwd_plan under the case's knob): the family and patch rows the
+    form's name claims, on the bias epilogue's Conv3d form."""
+    from avt_amd._lib import call
+
+    N, T, H, W, C, K, st = shape
+    plan = (ctypes.c_int * 10)()
+    with Halo3d(halo3d):
+        call("avt_conv_fwd_plan", N, T, H, W, C, K, 3, 3, 3, st, 1, 1, 2, plan)
+    family, rows_or_bk, opt, ksplit, epi = plan[0], plan[6], plan[7], plan[8], plan[9]
+    want_family, want_rows = NAMED.get(form, (2 if halo3d else 3, None))
+    assert (family, ksplit, epi) == (want_family, 1, 2), list(plan)
+    assert want_rows is None or rows_or_bk == want_rows, list(plan)
+    assert opt == (4 if family == 2 else 0), list(plan)
+
+
+@pytest.mark.parametrize("case", STEM_CASES)
+def test_stem_case_runs_the_long_tap_list_gather(case):
+    """The 49-tap stem: the tap-gather kernel on the bias epilogue's long-tap-list form."""
+    from avt_amd._lib import call
+
+    b, T, H, W = case
+    plan = (ctypes.c_int * 10)()
+    call("avt_conv_fwd_plan", b * T, 1, H, W, 32, 64, 1, 7, 7, 2, 0, 3, 2, plan)
+    assert (plan[0], plan[8], plan[9]) == (3, 1, 2), list(plan)
 
 
 def test_residual_rows_at_clip_boundaries():

@@ -36,8 +36,14 @@ FORMS = {
     # the 8-wave 256 x 128 tap-gather tile is the planner's choice from 65536 GEMM rows: the smallest such 1x1/s2 conv
     "gather_256x128": ({"avt_set_small_tiles": 0}, [(1, 511, 511, 64, 128, 1, 2)]),
 }
-RESTORE = {"avt_set_halo8": -1, "avt_set_small_tiles": -2, "avt_set_halo": 1, "avt_set_c64": 1}
+RESTORE = {"avt_set_halo8": -1, "avt_set_small_tiles": -2, "avt_set_halo": 1, "avt_set_c64": 1,
+           "avt_set_nt128_config": -1}
 CASES = [(f, s) for f, (_, shapes) in FORMS.items() for s in shapes]
+# what a form's name claims of avt_conv_fwd_plan's answer (include/avt_tuning.h): the family (0 c64, 1 halo, 3 tap
+# gather) and, where the name says one, the tile's rows x columns
+NAMED = {"c64": (0, None), "halo4": (1, (128, 128)), "halo8": (1, (256, 128)), "halo8x64": (1, (256, 64)),
+         "halo64": (1, (64, 128)), "gather_s2": (3, None), "gather_s1": (3, None), "gather_small": (3, (64, None)),
+         "gather_128x64": (3, (128, 64)), "gather_256x128": (3, (256, 128))}
 
 
 class Knobs:
@@ -118,6 +124,42 @@ def test_zero_bias_is_the_plain_forward(form, shape):
     with Knobs(FORMS[form][0]):
         y = _run(shape, x, w, torch.zeros_like(bias), None, False)
         y0 = _run(shape, x, w, None, None, False, entry="avt_conv2d_fwd")
+    assert torch.equal(y.view(torch.int16), y0.view(torch.int16))
+
+
+@pytest.mark.parametrize("form,shape", CASES)
+def test_case_runs_the_form_it_names(form, shape):
+    """The planner's own account of the call (avt_conv_fwd_plan under the case's knobs): the family and tile the form's
+    name claims, on the bias epilogue's narrow argument form, without split-K."""
+    from avt_amd._lib import call
+
+    N, H, W, C, K, k, stride = shape
+    plan = (ctypes.c_int * 10)()
+    with Knobs(FORMS[form][0]):
+        call("avt_conv_fwd_plan", N, 1, H, W, C, K, 1, k, k, stride, 0, k // 2, 1, plan)
+    family, wm, wn, tm, tn, _, _, _, ksplit, epi = plan
+    want_family, want_tile = NAMED[form]
+    tile = (wm * tm * 32, wn * tn * 32)
+    assert (family, ksplit, epi) == (want_family, 1, 1), list(plan)
+    assert want_tile is None or all(w is None or w == t for w, t in zip(want_tile, tile)), list(plan)
+
+
+def test_tile_override_does_not_reach_the_bias_epilogue():
+    """avt_set_nt128_config(3) moves the plain forward of this shape to the 256 x 128 k32 tile; the bias epilogue stays
+    on the planner's default (128 x 128 k64): with a zero bias it is, bit for bit, the plain forward at config -1."""
+    from avt_amd._lib import call
+
+    shape = (1, 7, 7, 256, 256, 3, 1)
+    x, w, bias, _, _ = _operands(shape)
+    base = {"avt_set_halo": 0, "avt_set_small_tiles": 0}
+    with Knobs(dict(base, avt_set_nt128_config=3)):
+        plan = (ctypes.c_int * 10)()
+        call("avt_conv_fwd_plan", 1, 1, 7, 7, 256, 256, 1, 3, 3, 1, 0, 1, 0, plan)
+        assert list(plan)[:7] == [3, 2, 2, 4, 2, 3, 32]  # the override is live for the plain forward
+        y = _run(shape, x, w, torch.zeros_like(bias), None, False)
+    with Knobs(base):
+        y0 = _run(shape, x, w, None, None, False, entry="avt_conv2d_fwd")
+    assert torch.isfinite(y.float()).all()
     assert torch.equal(y.view(torch.int16), y0.view(torch.int16))
 
 

@@ -66,7 +66,7 @@ CONV3D_CASES = [
     (2, 3, 112, 112, 64, 64, 1),
     (3, 2, 21, 30, 64, 64, 1),
     (1, 5, 56, 56, 128, 64, 1),
-    # the widths at which halo3d_launch changes its patch form, either side: 39 | 40 (336 rows | kHaloPR rows), 79 | 80
+    # the widths at which plan_nt changes the Conv3d halo patch form, either side: 39 | 40 (336 rows | kHaloPR rows), 79 | 80
     # (N % 128 == 0: the halo form | the tap gather), 115 | 116 (N = 64: 488 rows | the tap gather)
     (1, 2, 5, 39, 128, 128, 1),
     (1, 2, 5, 40, 128, 128, 1),
@@ -155,7 +155,7 @@ def test_conv3d_halo_two_tap_bitwise(case):
 @pytest.mark.parametrize("C,K", [(64, 64), (64, 128), (128, 128)])
 def test_conv3d_tile_configs(C, K):
     """Conv3d at a GEMM M >= 65536 (where the tile choice depends on K) under every tile config the
-    planner picks from (launch_nt): bitwise-equal outputs (the same k order per element), checked against
+    planner picks from (plan_nt): bitwise-equal outputs (the same k order per element), checked against
     torch on output frames 0-1."""
     N, T, H, W = 1, 8, 96, 96
     g = torch.Generator().manual_seed(12)
