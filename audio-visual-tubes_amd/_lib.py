@@ -80,6 +80,10 @@ SIGNATURES = {
     "avt_conv2d_wgrad_defer": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _Z,
                                     ctypes.POINTER(SlabReduceDesc), _P]),
     "avt_wgrad_reduce_batch": (_I, [ctypes.POINTER(SlabReduceDesc), _I, _P]),
+    "avt_set_wgrad_pixtab": (_I, [_I]),
+    "avt_wgrad_pixtab_bytes": (_Z, [_I, _I, _I, _I, _I, _I, _I]),
+    "avt_wgrad_pixtab_build": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "avt_wgrad_pixtab_register": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I]),
     "avt_bn_acc_doubles": (_Z, [_L, _I]),
     "avt_conv2d_fwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "avt_conv2d_fwd_bias": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P]),

@@ -13,6 +13,9 @@
 #include "avt_common.h"
 #include "avt_tuning.h"  // the knobs and avt_conv_fwd_plan defined here
 
+#include <mutex>
+#include <vector>
+
 namespace avt {
 
 #include "conv_params.h"
@@ -1856,12 +1859,75 @@ __global__ __launch_bounds__(256) void wgrad_slab_reduce_batch_kernel(SlabReduce
   }
 }
 
+// ---- per-pixel gather table of the tap-gather wgrad (conv_tn_pipe.h TAB) ----
+// One entry per output pixel, padded to a whole 32-pixel k-tile with always-invalid entries: {the byte offset of input
+// pixel (n, oh*stride - pad, ow*stride - pad) in the [N][H][W][Cp] bf16 tensor (32-bit, may wrap below zero: only valid
+// taps are dereferenced), a mask whose bit r*S + s says that tap (r, s) lands inside the image}.  Geometry only.
+__global__ __launch_bounds__(256) void wgrad_pixtab_kernel(uint2* __restrict__ tab, int npix, int npad, int P, int Q,
+                                                           int H, int W, int Cp, int R, int S, int stride, int pad) {
+  const int pix = blockIdx.x * 256 + threadIdx.x;
+  if (pix >= npad) return;
+  uint2 e = make_uint2(0u, 0u);
+  if (pix < npix) {
+    const int n = pix / (P * Q), rem = pix - n * (P * Q);
+    const int oh = rem / Q, ow = rem - oh * Q;
+    const int y0 = oh * stride - pad, x0 = ow * stride - pad;
+    e.x = (((unsigned)n * (unsigned)H + (unsigned)y0) * (unsigned)W + (unsigned)x0) * (unsigned)(Cp * 2);
+    for (int r = 0; r < R; ++r)
+      for (int s = 0; s < S; ++s)
+        if ((unsigned)(y0 + r) < (unsigned)H && (unsigned)(x0 + s) < (unsigned)W) e.y |= 1u << (r * S + s);
+  }
+  tab[pix] = e;
+}
+
+// A/B knob: AVT_WGRAD_PIXTAB / avt_set_wgrad_pixtab (1 default: a registered table is used; 0: the in-loop arithmetic).
+// Bitwise-equal results either way.
+static int g_wgrad_pixtab = -1;
+static int wgrad_pixtab_enabled() {
+  if (g_wgrad_pixtab < 0) g_wgrad_pixtab = getenv("AVT_WGRAD_PIXTAB") ? atoi(getenv("AVT_WGRAD_PIXTAB")) : 1;
+  return g_wgrad_pixtab;
+}
+
+// the tables the caller has built and keeps alive (avt_wgrad_pixtab_register), by device and geometry
+struct PixtabEntry {
+  int dev, N, H, W, Cp, R, S, stride, pad;
+  const void* tab;
+};
+static std::mutex g_pixtab_mu;
+static std::vector<PixtabEntry> g_pixtabs;
+
+static bool pixtab_geometry_ok(int N, int H, int W, int R, int S, int stride, int pad) {
+  if (N < 1 || H < 1 || W < 1 || R < 1 || S < 1 || R * S > 32 || (stride != 1 && stride != 2) || pad < 0) return false;
+  if (H + 2 * pad < R || W + 2 * pad < S) return false;
+  const long long npix = (long long)N * conv_out(H, R, stride, pad) * conv_out(W, S, stride, pad);
+  return npix >= 1 && (npix + 31) / 32 * 256 < (1ll << 31);
+}
+
+static const void* pixtab_lookup(int N, int H, int W, int Cp, int R, int S, int stride, int pad) {
+  if (!wgrad_pixtab_enabled()) return nullptr;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return nullptr;
+  std::lock_guard<std::mutex> lk(g_pixtab_mu);
+  for (const PixtabEntry& e : g_pixtabs)
+    if (e.dev == dev && e.N == N && e.H == H && e.W == W && e.Cp == Cp && e.R == R && e.S == S && e.stride == stride &&
+        e.pad == pad)
+      return e.tab;
+  return nullptr;
+}
+
 template <int WM, int WN, int TM, int TN, int NST, int KG>
 static void launch_tn_one(dim3 grid, const GemmTNPipeParams& pp, hipStream_t st) {
-  if (pp.cnt != nullptr)
-    hipLaunchKernelGGL((conv_tn_pipe_kernel<WM, WN, TM, TN, NST, KG, true>), grid, dim3(WM * WN * 64 * KG), 0, st, pp);
-  else
-    hipLaunchKernelGGL((conv_tn_pipe_kernel<WM, WN, TM, TN, NST, KG>), grid, dim3(WM * WN * 64 * KG), 0, st, pp);
+  const dim3 block(WM * WN * 64 * KG);
+  if (pp.tab != nullptr) {
+    if (pp.cnt != nullptr)
+      hipLaunchKernelGGL((conv_tn_pipe_kernel<WM, WN, TM, TN, NST, KG, true, true>), grid, block, 0, st, pp);
+    else
+      hipLaunchKernelGGL((conv_tn_pipe_kernel<WM, WN, TM, TN, NST, KG, false, true>), grid, block, 0, st, pp);
+  } else if (pp.cnt != nullptr) {
+    hipLaunchKernelGGL((conv_tn_pipe_kernel<WM, WN, TM, TN, NST, KG, true>), grid, block, 0, st, pp);
+  } else {
+    hipLaunchKernelGGL((conv_tn_pipe_kernel<WM, WN, TM, TN, NST, KG>), grid, block, 0, st, pp);
+  }
 }
 
 // the wgrad plan's launch shape runs the fused in-kernel slab reduce (launch_tn_one; the deeper-ring A/B variants
@@ -1887,6 +1953,11 @@ static void launch_tn(const WgradPlan& pl, float* slab, hipStream_t st, int* tic
     pp.cnt = (slab != nullptr && tickets != nullptr && tn_fusable(pl)) ? tickets : nullptr;
     pp.slab_bytes = (unsigned)pl.slab_bytes;
     pp.splits = pl.splits;
+    // the registered per-pixel table of this geometry (launch_tn_one's instantiations read it; the deeper-ring A/B
+    // variants below keep the in-loop arithmetic)
+    pp.tab = pixtab_geometry_ok(p.Kred / (p.P * p.Q), p.H, p.W, p.R, p.S, p.stride, p.pad)
+                 ? pixtab_lookup(p.Kred / (p.P * p.Q), p.H, p.W, p.Cp, p.R, p.S, p.stride, p.pad)
+                 : nullptr;
     const dim3 grid(pl.tiles * pl.splits);
     if constexpr (BM == 256 && BN == 256) {
       if (pl.nst >= 5)
@@ -2104,6 +2175,53 @@ extern "C" int avt_set_wgrad_row3(int kg, int min_kt, int pf) {
   g_row3_kg = kg;
   g_row3_min_kt = min_kt;
   g_row3_pf = pf;
+  return AVT_OK;
+}
+
+extern "C" int avt_set_wgrad_pixtab(int on) {
+  AVT_REQUIRE(on >= -1 && on <= 1, "avt_set_wgrad_pixtab: %d (0 in-loop arithmetic, 1 registered tables, -1 env "
+              "AVT_WGRAD_PIXTAB)", on);
+  g_wgrad_pixtab = on;
+  return AVT_OK;
+}
+
+extern "C" size_t avt_wgrad_pixtab_bytes(int N, int H, int W, int R, int S, int stride, int pad) {
+  using namespace avt;
+  if (!pixtab_geometry_ok(N, H, W, R, S, stride, pad)) return 0;
+  const long long npix = (long long)N * conv_out(H, R, stride, pad) * conv_out(W, S, stride, pad);
+  return (size_t)((npix + 31) / 32 * 32) * 8;
+}
+
+extern "C" int avt_wgrad_pixtab_build(void* tab, int N, int H, int W, int Cp, int R, int S, int stride, int pad,
+                                      void* stream) {
+  using namespace avt;
+  AVT_REQUIRE(tab, "wgrad_pixtab_build: null table");
+  AVT_REQUIRE(Cp >= 1 && pixtab_geometry_ok(N, H, W, R, S, stride, pad),
+              "wgrad_pixtab_build: no table form for this geometry (at most 32 taps, stride 1 or 2)");
+  const int P = conv_out(H, R, stride, pad), Q = conv_out(W, S, stride, pad);
+  const int npix = N * P * Q, npad = (npix + 31) / 32 * 32;
+  hipLaunchKernelGGL(wgrad_pixtab_kernel, dim3((npad + 255) / 256), dim3(256), 0, (hipStream_t)stream, (uint2*)tab,
+                     npix, npad, P, Q, H, W, Cp, R, S, stride, pad);
+  return check_launch("wgrad_pixtab_build");
+}
+
+extern "C" int avt_wgrad_pixtab_register(const void* tab, int N, int H, int W, int Cp, int R, int S, int stride,
+                                         int pad) {
+  using namespace avt;
+  AVT_REQUIRE(Cp >= 1 && pixtab_geometry_ok(N, H, W, R, S, stride, pad),
+              "wgrad_pixtab_register: no table form for this geometry (at most 32 taps, stride 1 or 2)");
+  int dev = 0;
+  AVT_REQUIRE(hipGetDevice(&dev) == hipSuccess, "wgrad_pixtab_register: no current device");
+  std::lock_guard<std::mutex> lk(g_pixtab_mu);
+  for (size_t i = 0; i < g_pixtabs.size(); ++i) {
+    const PixtabEntry& e = g_pixtabs[i];
+    if (e.dev == dev && e.N == N && e.H == H && e.W == W && e.Cp == Cp && e.R == R && e.S == S && e.stride == stride &&
+        e.pad == pad) {
+      g_pixtabs.erase(g_pixtabs.begin() + (long)i);
+      break;
+    }
+  }
+  if (tab != nullptr) g_pixtabs.push_back(PixtabEntry{dev, N, H, W, Cp, R, S, stride, pad, tab});
   return AVT_OK;
 }
 

@@ -64,6 +64,13 @@ __device__ __forceinline__ void buf_lds16_at(__amdgpu_buffer_rsrc_t rs, unsigned
                : "memory");
 }
 
+// one dword per lane (the TN wgrad's per-pixel table slots: conv_tn_pipe.h)
+__device__ __forceinline__ void buf_lds4_at(__amdgpu_buffer_rsrc_t rs, unsigned lds_addr, unsigned voff) {
+  const unsigned lds = __builtin_amdgcn_readfirstlane(lds_addr);
+  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dword %1, %2, 0 offen lds" ::"s"(lds), "v"(voff), "s"(rs)
+               : "memory");
+}
+
 // write-through (sc1) 16-byte stores / loads of the split-K partial tiles: the hand-off of
 // MI355X_MICROARCH.md's table (sc1 stores, every storing wave's vmcnt(0), a barrier, one agent-scope
 // atomic add per workgroup; the last adder reads with sc1 loads) -- no L2 write-back fence needed

@@ -8,8 +8,20 @@
 // (chunk ^ f(row)) so that the ds_read_b64_tr_b16 fragment reads are bank-conflict-free.  The
 // images are filled with `buffer_load_dwordx4 ... lds` (lane-linear; the swizzle goes on the
 // source chunk).  Each lane owns one fixed logical chunk (a fixed k_out block for DY, a fixed
-// (r,s,c) patch column block for X); per k-tile it decomposes its pixel(s) with magic-number
-// divisions.  NST-stage ring, NST-1 tiles in flight, split-K over blockIdx.y, fp32 atomics.
+// (r,s,c) patch column block for X).  NST-stage ring, NST-1 tiles in flight, split-K over blockIdx.y, fp32 atomics.
+//
+// Where a gathered X row comes from, two forms with the same offsets and the same zeros (bitwise-equal results):
+//   - in-loop arithmetic (TAB = false; also the ring's prologue of the table form): per B instruction and k-tile the
+//     lane advances its pixel (ow, oh, image base) by 32, forms the tap's input coordinates, tests both bounds and
+//     multiplies out the byte offset: about 20 VALU per instruction, as many issue cycles as the MFMAs beside them;
+//   - per-pixel table (TAB = true, GemmTNPipeParams::tab, built once per conv geometry by avt_wgrad_pixtab_build):
+//     entry[pix] = {byte offset of the pixel's tap-(0,0) input position, mask of the taps inside the image}.  A lane
+//     keeps its constant column part r*rowB + s*pixB + c*2 and its tap's mask bit (0 for a column past R*S*Cp); per
+//     B instruction and k-tile it reads one 8-byte entry from LDS, adds, tests the bit and selects kOOB.  The entries
+//     reach LDS by one more LDS-DMA per wave and tile on the same counted vmcnt ring (see the kernel's comment):
+//     no VGPR-destination load beside the DMAs, nothing for the compiler's own waits to drain.
+//     Measured at 128 clips (profiles/pixtab_wgrad_b128.txt): VALU per MFMA 8.1 -> 3.7 (128 x 128, two k groups) and
+//     5.2 -> 2.9 (256 x 256), SALU per MFMA 3.6 -> 2.3 and 1.9 -> 1.2; the launches 10-11 % shorter.
 #pragma once
 
 // (MagicDiv, make_magic, magic_div: avt_common.h)
@@ -24,6 +36,10 @@ struct GemmTNPipeParams {
   int* cnt;
   unsigned slab_bytes;
   int splits;
+  // per-pixel gather table (avt_wgrad_pixtab_build: [ceil(Kred / 32) * 32] x {u32 byte offset of the pixel's tap-(0,0)
+  // input position, u32 mask with bit r*S + s set where tap (r, s) lands inside the image}), read by the TAB
+  // instantiations; null: the in-loop pixel arithmetic
+  const void* tab;
 };
 
 template <int ROWB>
@@ -38,7 +54,17 @@ __device__ __forceinline__ int tn_swz(int row) {  // chunk XOR for a row of ROWB
 // FUSED: the split-K slab is reduced by the last block of each tile (write-through partial stores, one agent-scope
 // ticket per block, the last reads the partials back in split order -- the order wgrad_slab_reduce_native_kernel uses
 // with G = 1, so the two paths give the same bits); every block of the grid takes a ticket, an empty k range included
-template <int WM, int WN, int TM, int TN, int NST, int KG = 1, bool FUSED = false>
+// TAB: the B operand's gather offsets come from the per-pixel table instead of the in-loop pixel arithmetic.  Each
+// wave DMAs the 32 / NW table entries of ITS rows of a k-tile into a 256-byte LDS slot of its own (one
+// `buffer_load_dword ... lds`: lanes 0 .. 2 * 32/NW - 1 fetch the entries' dwords, the others an out-of-range zero),
+// NST - 1 steps ahead of the step that gathers that tile, as one more load of the counted vmcnt ring: the groups
+// [A(t), B(t), table(t + NST - 1)] are issued in order, so the wait that retires tile k's operands also retires the
+// table of tile k + NST - 1, which the step then reads (ds_read_b64) for its B instructions: offset = entry.x +
+// the lane's constant column part, valid = entry.y & the lane's tap bit.  The table's buffer range ends at the
+// group's last live tile, so dummy tiles read all-zero (all-invalid) entries; the padded entries past the batch are
+// invalid too.  The first NST - 1 tiles (the prologue) keep the arithmetic: no table wait before the first DMA.
+// The same offsets and the same zeros as the arithmetic: bitwise-equal results.
+template <int WM, int WN, int TM, int TN, int NST, int KG = 1, bool FUSED = false, bool TAB = false>
 __global__ __launch_bounds__(WM * WN * 64 * KG) void conv_tn_pipe_kernel(GemmTNPipeParams pp) {
   constexpr int NW = WM * WN;  // waves per group
   static_assert(KG == 1 || KG == 2, "one or two k groups");
@@ -50,9 +76,11 @@ __global__ __launch_bounds__(WM * WN * 64 * KG) void conv_tn_pipe_kernel(GemmTNP
   constexpr int A_RPI = 1024 / AROWB, B_RPI = 1024 / BROWB;  // rows per 1 KiB instruction
   constexpr int AI = 32 / A_RPI / NW, BI = 32 / B_RPI / NW;  // instructions per wave per tile
   static_assert(AI >= 1 && BI >= 1 && AI * A_RPI * NW == 32 && BI * B_RPI * NW == 32, "tile/wave split");
-  constexpr int LPT = AI + BI;
+  constexpr int LPT = AI + BI + (TAB ? 1 : 0);  // loads per wave per tile (TAB: + the table slot's DMA)
   constexpr int A_BYTES = 32 * AROWB, STAGE = 32 * (AROWB + BROWB);
-  __shared__ __attribute__((aligned(16))) char smem_all[KG * NST * STAGE];
+  constexpr int RPW = 32 / NW;                             // B rows (table entries) per wave per tile
+  constexpr int TAB_BASE = KG * NST * STAGE;               // the table slots follow the rings: [wave][NST][256 B]
+  __shared__ __attribute__((aligned(16))) char smem_all[TAB_BASE + (TAB ? KG * NW * NST * 256 : 0)];
   const GemmTNParams& p = pp.p;
 
   const int tid = threadIdx.x, lane = tid & 63;
@@ -101,6 +129,7 @@ __global__ __launch_bounds__(WM * WN * 64 * KG) void conv_tn_pipe_kernel(GemmTNP
   int b_oh[BI], b_ow[BI], y_off[BI], x_off[BI];
   unsigned b_nb[BI], cB[BI];
   bool b_colok[BI];
+  unsigned t_col[BI], t_bit[BI];  // TAB: r*rowB + s*pixB + c*2 and the tap's mask bit (0: a column past R*S*Cp)
 #pragma unroll
   for (int i = 0; i < BI; ++i) {
     const int row = (wid * BI + i) * B_RPI + b_r;
@@ -112,6 +141,8 @@ __global__ __launch_bounds__(WM * WN * 64 * KG) void conv_tn_pipe_kernel(GemmTNP
     y_off[i] = b_rr - p.pad;
     x_off[i] = b_colok[i] ? b_ss - p.pad : (1 << 20);  // a column past R*S*C: always out of the image
     cB[i] = (unsigned)(b_c * 2);
+    t_col[i] = (unsigned)b_rr * rowB + (unsigned)b_ss * pixB + cB[i];
+    t_bit[i] = b_colok[i] ? 1u << (rs & 31) : 0u;
     const int pix = kt_begin * 32 + row;
     const unsigned n = magic_div((unsigned)pix, pp.div_pq);
     const unsigned rem = (unsigned)pix - n * (unsigned)(p.P * p.Q);
@@ -170,6 +201,45 @@ __global__ __launch_bounds__(WM * WN * 64 * KG) void conv_tn_pipe_kernel(GemmTNP
     }
   };
 
+  // TAB: this wave's table slots, the table's buffer (its range ends with the group's last live tile) and the
+  // wave's running source offset (the table DMAs go tile by tile, 256 table bytes each)
+  const unsigned tab_lds = (unsigned)(size_t)(lds_void_t*)smem_all + (unsigned)(TAB_BASE + wtot * (NST * 256));
+  const char* const tab_rd = smem_all + TAB_BASE + wtot * (NST * 256) + b_r * 8;
+  const int tab_tiles = TAB ? min(kt_end, nkt_total) : 0;
+  const __amdgpu_buffer_rsrc_t rst =
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(pp.tab), (short)0, tab_tiles * 256, 0x00020000);
+  unsigned tab_voff = lane < 2 * RPW ? (unsigned)((kt_begin + NST - 1) * 256 + wid * (RPW * 8) + lane * 4) : kOOB;
+  auto tab_dma = [&](int slot) {  // the next tile's entries of this wave's rows into `slot`
+    buf_lds4_at(rst, tab_lds + (unsigned)(slot * 256), tab_voff);
+    tab_voff += 256u;  // (an out-of-range lane stays out of range: 2^31 + 256 * tiles)
+  };
+  uint2 te[BI];  // the entries of the tile about to be gathered
+  auto tab_read = [&](int slot) {
+#pragma unroll
+    for (int i = 0; i < BI; ++i) te[i] = *reinterpret_cast<const uint2*>(tab_rd + slot * 256 + i * (B_RPI * 8));
+  };
+  // both words of every entry are in registers here (left to itself the compiler reads the offset word in a branch
+  // under the tap test: an exec-mask branch and a second LDS round trip per B instruction)
+  auto tab_pin = [&]() {
+#pragma unroll
+    for (int i = 0; i < BI; ++i) asm volatile("" : "+v"(te[i].x), "+v"(te[i].y));
+  };
+  auto issue_tab = [&](int kt, int stage) {  // as issue(), with the B offsets from te[]
+    const unsigned As = smem_lds + (unsigned)(stage * STAGE);
+    const unsigned Bs = As + A_BYTES;
+    const bool live = kt < kt_end;
+#pragma unroll
+    for (int i = 0; i < AI; ++i) {
+      buf_lds16_at(rsa, As + (unsigned)((wid * AI + i) * 1024), live ? a_off[i] : kOOB);
+      a_off[i] += a_step;
+    }
+#pragma unroll
+    for (int i = 0; i < BI; ++i) {
+      const unsigned off = te[i].x + t_col[i];
+      buf_lds16_at(rsb, Bs + (unsigned)((wid * BI + i) * 1024), (te[i].y & t_bit[i]) != 0u ? off : kOOB);
+    }
+  };
+
   f32x16 acc[TM][TN];
 #pragma unroll
   for (int i = 0; i < TM; ++i)
@@ -186,7 +256,10 @@ __global__ __launch_bounds__(WM * WN * 64 * KG) void conv_tn_pipe_kernel(GemmTNP
   typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 
 #pragma unroll
-  for (int s = 0; s < NST - 1; ++s) issue(kt_begin + s, s);
+  for (int s = 0; s < NST - 1; ++s) {
+    issue(kt_begin + s, s);
+    if constexpr (TAB) tab_dma((NST - 1 + s) % NST);  // tile kt_begin + NST - 1 + s, gathered by step s
+  }
 
   bf16x8 af[2][TM], bfr[2][TN];  // fragments of k-step ks live in [ks & 1]
   auto load_frags = [&](const char* As, const char* Bs, int ks, int buf) {
@@ -223,8 +296,16 @@ __global__ __launch_bounds__(WM * WN * 64 * KG) void conv_tn_pipe_kernel(GemmTNP
     ring_barrier();
     const char* As = smem + rs * STAGE;
     const char* Bs = As + A_BYTES;
+    if constexpr (TAB) tab_read(is);  // tile k + NST - 1's entries: slot (k + NST - 1) % NST (ahead of the fragments:
+                                      // LDS reads return in order, and the DMA issue below waits for these)
     load_frags(As, Bs, 0, 0);
-    issue(kt_begin + k + NST - 1, is);
+    if constexpr (TAB) {
+      tab_pin();
+      issue_tab(kt_begin + k + NST - 1, is);
+      tab_dma((is + NST - 1) % NST);  // tile k + 2 NST - 2's entries into the slot step k - 1 read
+    } else {
+      issue(kt_begin + k + NST - 1, is);
+    }
     // step 1's fragments are read while step 0 multiplies
     load_frags(As, Bs, 1, 1);
     __builtin_amdgcn_sched_barrier(0);

@@ -39,6 +39,38 @@ def stream_ptr():
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+# The tap-gather wgrad's per-pixel gather tables (avt_wgrad_pixtab_*, include/avt.h): geometry only, so one per device
+# and (N, H, W, Cp, k, stride, pad), built at the first wgrad of that geometry outside a graph capture, registered with
+# the library and kept alive here for the life of the process; convs of one geometry share it.
+_PIXTABS: Dict = {}
+
+
+def wgrad_pixtab(device: torch.device, N: int, H: int, W: int, cp: int, k: int, stride: int, pad: int):
+    """The registered table of a wgrad geometry (built and registered at first use), or None: no table form for it
+    (the stems), a library without the entry points, or a first use inside a graph capture (the wgrad then runs its
+    in-loop arithmetic: the same bits)."""
+    key = (device.index if device.index is not None else torch.cuda.current_device(), N, H, W, cp, k, stride, pad)
+    if key in _PIXTABS:
+        return _PIXTABS[key]
+    from ._lib import lib
+    if cp % 8 != 0 or not hasattr(lib(), "avt_wgrad_pixtab_build"):
+        _PIXTABS[key] = None
+        return None
+    nbytes = int(query("avt_wgrad_pixtab_bytes", N, H, W, k, k, stride, pad))
+    if nbytes == 0:
+        _PIXTABS[key] = None
+        return None
+    if torch.cuda.is_current_stream_capturing():
+        return None
+    with torch.cuda.device(key[0]):
+        tab = torch.empty(nbytes // 4, device=device, dtype=torch.int32)
+        call("avt_wgrad_pixtab_build", P(tab), N, H, W, cp, k, k, stride, pad, stream_ptr())
+        torch.cuda.current_stream().synchronize()  # once per geometry: any stream may read it from here on
+        call("avt_wgrad_pixtab_register", P(tab), N, H, W, cp, k, k, stride, pad)
+    _PIXTABS[key] = tab
+    return tab
+
+
 def drive(gen):
     """Run a launch generator (Trunk.*_iter) to completion; return its value."""
     while True:
@@ -447,6 +479,7 @@ class Trunk:
         ws = torch.empty(wsb, device=x.device, dtype=torch.uint8) if wsb else None
         pending = store.wgrad_pending(self.prefix) if ws is not None else None
         tk = store.wgrad_tickets(spec, N, H, W) if ws is not None and pending is None else None
+        wgrad_pixtab(x.device, N, H, W, spec.cp, spec.k, spec.stride, spec.pad)  # planned once per geometry
         ev = ConvProfiler.begin()
         if pending is not None:
             d = SlabReduceDesc()

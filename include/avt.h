@@ -184,6 +184,22 @@ int avt_conv2d_wgrad_tickets(int N, int H, int W, int Cp, int Creal, int K, int 
 int avt_conv2d_wgrad_tk(const void* x, const void* dy, float* dw, int N, int H, int W, int Cp, int Creal, int K, int R,
                         int S, int stride, int pad, void* workspace, size_t ws_bytes, int* tickets, int n_tickets,
                         void* stream);
+/* Per-pixel gather table of the tap-gather wgrad (3x3 / 1x1 convs with Cp % 8 == 0; the stems have their own kernel).
+ * One 8-byte entry per output pixel (n, oh, ow), pixel-major, padded with always-invalid (0, 0) entries to a multiple
+ * of 32 pixels: a u32 byte offset of input pixel (n, oh*stride - pad, ow*stride - pad) in x[N][H][W][Cp] bf16 (modulo
+ * 2^32: it may lie before the tensor; only taps inside the image are dereferenced) and a u32 mask whose bit r*S + s is
+ * set where tap (r, s) of that pixel lands inside the image.  It depends on the geometry only -- not on x's address, not
+ * on the weights -- so it is built once per geometry and shared by every conv of that geometry:
+ *   avt_wgrad_pixtab_bytes()    the table's size, 0 where the form does not apply (more than 32 taps)
+ *   avt_wgrad_pixtab_build()    fills `tab` (a launch on `stream`: never inside a graph capture, never per step)
+ *   avt_wgrad_pixtab_register() tells the wgrad entry points above to read `tab` for this geometry on the current
+ *                               device; the caller keeps it alive and unchanged until it registers NULL (or another
+ *                               table) for the geometry.
+ * With a registered table the wgrad kernel loads its gather offsets instead of recomputing them per k-tile: the same
+ * products in the same order, bitwise-equal results (avt_set_wgrad_pixtab(0), include/avt_tuning.h, ignores the tables). */
+size_t avt_wgrad_pixtab_bytes(int N, int H, int W, int R, int S, int stride, int pad);
+int avt_wgrad_pixtab_build(void* tab, int N, int H, int W, int Cp, int R, int S, int stride, int pad, void* stream);
+int avt_wgrad_pixtab_register(const void* tab, int N, int H, int W, int Cp, int R, int S, int stride, int pad);
 
 /* Input gradient of the 7x7 / stride 2 / pad 3 stem conv (base_models.py:135-138, the reference's autograd through
  * conv1 / conv1_a when the trunk input requires grad): gx[N][Cin][H][W] fp32 (NCHW, the input's layout) =

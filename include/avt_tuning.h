@@ -88,6 +88,11 @@ int avt_set_halo_tps2(int on);
  * max_kb KiB (env AVT_WGRAD_FUSED_MAX_KB, default 2048); 0 (default, env AVT_WGRAD_FUSED) = the separate reduce launch
  * (measured faster); -1: back to the environment default */
 int avt_set_wgrad_fused(int on, int max_kb);
+/* A/B knob, 1 by default (env AVT_WGRAD_PIXTAB): the tap-gather wgrad reads the per-pixel gather table registered for
+ * its geometry (avt_wgrad_pixtab_register, include/avt.h) -- one 8-byte entry, an add, a bit test and a select per
+ * gathered row and k-tile; 0: it recomputes the pixel coordinates, bounds and offsets in the loop (also what a geometry
+ * without a registered table runs); -1: back to the environment default.  Bitwise-equal results either way */
+int avt_set_wgrad_pixtab(int on);
 /* 1 (default, env AVT_STEM): the 7x7/s2 stem forwards (C 4 or 1, K 64) run on the per-wave LDS-patch
  * stem kernel (BN statistics of the stored bf16 tensor, on the MFMA pipe); 0: the generic gather kernel */
 int avt_set_stem_kernel(int on);
