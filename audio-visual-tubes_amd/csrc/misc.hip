@@ -635,6 +635,7 @@ extern "C" int avt_adam_apply_dev(float* param, const float* grad, float* exp_av
 
 extern "C" int avt_nchw_to_nhwc_bf16(const float* x, void* y, int N, int C, int H, int W, int Cp, void* stream) {
   AVT_REQUIRE(x && y && Cp >= C, "nchw_to_nhwc_bf16: bad arguments");
+  AVT_REQUIRE(Cp != 4 || ((uintptr_t)y & 7) == 0, "nchw_to_nhwc_bf16: y must be 8-byte aligned");
   if (nhwc4_ok(x, y, N, C, 1, H, W, Cp)) {
     const int total4 = (int)((long long)N * H * W / 4);
     if (Cp == 4)

@@ -95,6 +95,9 @@ class _FlipLossFn(torch.autograd.Function):
         if heatmap.shape != flipped.shape or heatmap.dim() < 1:
             raise ValueError(f"avt: FlipLoss needs two tensors of one shape, got {tuple(heatmap.shape)} and "
                              f"{tuple(flipped.shape)}")
+        if heatmap.numel() == 0:
+            raise ValueError(f"avt: FlipLoss of an empty tensor {tuple(heatmap.shape)} (the reference's mean over "
+                             "no elements is NaN)")
         x = heatmap.detach().contiguous().float()
         y = flipped.detach().contiguous().float()
         W = x.shape[-1]

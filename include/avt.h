@@ -506,6 +506,8 @@ int avt_pack_conv_weights_part(const void* descs, int n, long long max_elems, in
  * takes.  max_elems: the largest K*Kg of the records.  Reads nothing it writes; no host sync; deterministic. */
 size_t avt_fold_desc_bytes(void);
 int avt_fold_conv_bn_batched(const void* descs, int n, long long max_elems, void* stream);
+/* x [N][C][H][W] fp32 -> y [N][H][W][Cp] bf16 (round to nearest even, channels >= C zero).  With Cp = 4 y must be
+ * 8-byte aligned, here and in avt_ncthw_to_nhwc_bf16: a pixel's four channels are stored at once. */
 int avt_nchw_to_nhwc_bf16(const float* x, void* y, int N, int C, int H, int W, int Cp, void* stream);
 /* x [N][C][T][H][W] fp32 -> y [(N T)][H][W][Cp] bf16: the 'b c t h w -> (b t) c h w' fold of
  * train_hardway.py:130-131 fused with the NHWC/bf16 conversion */
