@@ -161,6 +161,9 @@ SIGNATURES = {
     "avt_spectrogram_segments": (_I, [_L, _I]),
     "avt_spectrogram": (_I, [_P, _I, _L, _I, _F, _P, _P]),
     "avt_frames_transform": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "avt_clip_crop2": (_I, [_I]),
+    "avt_clip_workspace_bytes": (_Z, [_I, _I, _I, _I, _I]),
+    "avt_clip_transform": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _Z, _P, _P, _P, _P, _P]),
     "avt_adam_step": (_I, [_P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _F, _I, _P]),
     "avt_adam_step_dev": (_I, [_P, _P, _P, _P, _L, _F, _P, _P, _P, _P]),
     "avt_adam_prep_dev": (_I, [_P, _P, _P, _P]),

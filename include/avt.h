@@ -48,6 +48,8 @@
  *   avt_spectrogram              the dataset's scipy.signal.spectrogram + log + Normalize(0, 12)
  *   avt_frames_transform         the dataset's frame transform: PIL BICUBIC Resize + crop + flip + ToTensor +
  *                                Normalize (datasets/dataloader.py:47-62)
+ *   avt_clip_transform           the two-view dataset's clip transform: clip-consistent Resize / crop / flip, and the
+ *                                crop + ColorJitter + Resize + flip of the second view (datasets/dataloader.py:155-181)
  *                                (datasets/dataloader.py:86-96, 252-274)
  */
 #ifndef AVT_H_
@@ -472,6 +474,41 @@ int avt_spectrogram(const float* x, int B, long long N, int hop, float fs, float
  * (fixed-point separable resampler); S <= 256, downscale factor <= 7.5 (checked by the caller). */
 int avt_frames_transform(const void* src, const long long* desc, int n, int S, int Hmax, void* tmp,
                          const float* mean, const float* std, float* out, void* stream);
+
+/* ---- two-view clip transform (SubSampledFlickr, datasets/dataloader.py:155-181, 260-263) ----
+ * b clips of t frames each (frame k of clip i is entry i*t + k of src / desc) -> the two tensors of the 16-frame
+ * two-view step, float32 NCTHW [b][3][t][S][S]:
+ *   frames    = Resize(bicubic) -> crop(S) -> flip -> ToTensor -> Normalize         (desc, as avt_frames_transform;
+ *               the caller repeats a clip's draw in each of its frames' rows)
+ *   augmented = crop(S2 = avt_clip_crop2(S) = int(0.7 S)) of the 8-bit `frames` image -> colour jitter -> Resize(S,
+ *               bicubic) -> flip -> ToTensor -> Normalize                            (view2[i], one per clip)
+ * The jitter is an ordered chain of at most four ops, each kind at most once, each acting on the previous op's 8-bit
+ * result, in Pillow's arithmetic (ImageEnhance.Brightness / Contrast / Color; hue through convert("HSV") with
+ * H' = (H + int(255 h)) mod 256, |h| <= 0.5); the contrast mean is per frame, the factor per clip.  Bit-identical
+ * to the same pipeline done with Pillow 12.2.0.  view2 == NULL and augmented == NULL: `frames` alone (test mode).
+ * desc and view2 are DEVICE tables; mean / std HOST float[3].  Five launches (two for one view), whatever b and t;
+ * no atomics.  The checks of avt_frames_transform's caller apply (crop inside the resized frame, downscale <= 7.5,
+ * Hmax >= every H), and 0 <= crop_top, crop_left <= S - S2.  workspace: >= avt_clip_workspace_bytes() bytes,
+ * 16-byte aligned, any contents; desc / view2 8-byte aligned.  AVT_EINVAL on a bad size, a short workspace or a
+ * misaligned pointer. */
+#define AVT_JITTER_BRIGHTNESS 0
+#define AVT_JITTER_CONTRAST 1
+#define AVT_JITTER_SATURATION 2
+#define AVT_JITTER_HUE 3
+typedef struct {
+  int kind; /* AVT_JITTER_* */
+  int reserved;
+  double factor; /* brightness / contrast / saturation: >= 0 (1 = unchanged); hue: h in [-0.5, 0.5] */
+} avt_jitter_op;
+typedef struct {
+  int crop_top, crop_left, flip, nops;
+  avt_jitter_op ops[4];
+} avt_clip_view2; /* 80 bytes */
+int avt_clip_crop2(int S);
+size_t avt_clip_workspace_bytes(int b, int t, int S, int Hmax, int two_views);
+int avt_clip_transform(const void* src, const long long* desc, const avt_clip_view2* view2, int b, int t, int S,
+                       int Hmax, void* workspace, size_t ws_bytes, const float* mean, const float* std, float* frames,
+                       float* augmented, void* stream);
 
 /* ---- optimizer / layout ---- */
 int avt_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long long n, float grad_scale,
