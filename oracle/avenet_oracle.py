@@ -131,6 +131,19 @@ def make_gout(batch: int, h: int, w: int, seed: int = 7) -> torch.Tensor:
     return g.to(torch.bfloat16).float()
 
 
+def make_cot(batch: int, h: int, w: int, scale: float = 1.0, maps: bool = True, seed: int = 11) -> dict:
+    """Fixed cotangents of the one-frame step's outputs for avenet_forced_grads: "scale" multiplies CE(logits, 0);
+    with maps, dense standard-normal "wA" [batch,h,w] and "A", "Pos", "Neg" [batch,1,h,w] (fp32, as the head's
+    backward takes them), else None."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    cot = {"scale": scale, "wA": None, "A": None, "Pos": None, "Neg": None}
+    if maps:
+        cot["wA"] = torch.from_numpy(rng.standard_normal((batch, h, w), dtype=np.float32))
+        for k in ("A", "Pos", "Neg"):
+            cot[k] = torch.from_numpy(rng.standard_normal((batch, 1, h, w), dtype=np.float32))
+    return cot
+
+
 def make_spectrogram(batch: int, freq: int = 257, frames: int = 300, seed: int = 2) -> torch.Tensor:
     """log-spectrogram recipe of datasets/dataloader.py:86-96 on clipped Gaussian noise.
 
@@ -504,3 +517,131 @@ def make_frames(b: int, t: int, size: int = 224, seed: int = 3) -> torch.Tensor:
     """Seeded synthetic clip frames [b,3,t,H,W] (ImageNet-normalised range, like make_image)."""
     rng = np.random.Generator(np.random.PCG64(seed))
     return torch.from_numpy(rng.standard_normal((b, 3, t, size, size), dtype=np.float32))
+
+
+# --------------------------------------------------------------------------------------
+# the whole step's backward on a recorded forward ("forced tape")
+# --------------------------------------------------------------------------------------
+
+STEP_FAULTS = ("detach_audio", "const_norm", "pool_spread", "ce_sum", "gan_overwrite")
+
+
+def _forced_leaves(sd):
+    """(names, {name: fp64 leaf}) of trainable_names(sd): conv weights at their bf16-rounded values (the operands the
+    trunks compute with), BN parameters as they are."""
+    names = trainable_names(sd)
+    s = {}
+    for n in names:
+        v = sd[n].detach()
+        v = v.to(torch.bfloat16) if v.dim() == 4 else v
+        s[n] = v.to(torch.float64).clone().requires_grad_(True)
+    return names, s
+
+
+def _bf16_leaf(x: torch.Tensor) -> torch.Tensor:
+    return x.detach().to(torch.bfloat16).to(torch.float64).requires_grad_(True)
+
+
+def _tape64(tape: dict) -> dict:
+    out = {k: v.double() for k, v in tape.items() if k != "blocks"}
+    out["blocks"] = [{k: v.double() for k, v in tb.items()} for tb in tape["blocks"]]
+    return out
+
+
+def _grad_or_zero(t: torch.Tensor) -> torch.Tensor:
+    return t.grad if t.grad is not None else torch.zeros_like(t)  # (a fault may cut a leaf off the graph)
+
+
+def _forced_audio_vectors(s, ain, tape_aud, amax, rnd, fault):
+    """The audio trunk forced onto its tape, the global max-pool AT THE RECORDED POSITIONS amax [B,C] (row index
+    y * w + x of the layer4 map), F.normalize: the unit vectors [B,C].  The recorded position must hold the channel's
+    maximum: among equal bf16 maxima the gradient then goes where the recorded forward sent it."""
+    a = resnet18_forward_forced(s, "audnet.", ain, "audio", _tape64(tape_aud), grad_round=rnd)
+    flat = a.flatten(2)
+    pooled = flat.gather(2, amax.long().unsqueeze(-1)).squeeze(-1)
+    assert torch.equal(pooled.detach(), flat.detach().amax(-1)), "amax does not point at the channel maxima"
+    if fault == "pool_spread":
+        mean = flat.mean(-1)
+        pooled = mean + (pooled - mean).detach()
+    an = F.normalize(pooled, dim=1)
+    return an.detach() if fault == "detach_audio" else an
+
+
+def _forced_vision_map(s, xin, tape_img, rnd, fault):
+    """The vision trunk forced onto its tape, L2-normalised over channels.  (The gradient of the stored map v is
+    rounded by rnd: v is block 7's output, one of the tensors resnet18_forward_forced hooks.)"""
+    v = resnet18_forward_forced(s, "imgnet.", xin, "vision", _tape64(tape_img), grad_round=rnd)
+    if fault == "const_norm":
+        return v / v.detach().norm(dim=1, keepdim=True).clamp_min(1e-12)
+    return F.normalize(v, dim=1)
+
+
+def _bf16_round(g):
+    return g.to(torch.bfloat16).to(g.dtype)
+
+
+def avenet_forced_grads(sd, image, audio, tape: dict, cot: dict, round_grads: bool = False, fault: str = None,
+                        args: Args = None, tau: float = 0.03):
+    """The one-frame step's backward on a recorded forward: {name: fp64 gradient} for trainable_names(sd), plus
+    "image" and "audio" (the input gradients at the bf16-rounded inputs), of
+        cot.scale * CE(logits, 0) + <cot.wA, weighted_A> + <cot.A, A> + <cot.Pos, Pos> + <cot.Neg, Neg>
+    (make_cot; a None cotangent drops its term) with both trunks teacher-forced (resnet18_forward_forced) onto
+    tape["img"] / tape["aud"] (NCHW: c0, p0, blocks), so that the head sees exactly the recorded layer4 maps, the
+    audio pool taken at tape["amax"] [B,C], and the head (F.normalize, hardway_head with args and tau) in fp64.
+    round_grads: the yardstick -- every activation gradient the trunks store in bf16 is rounded to bf16 (the set
+    resnet18_forced_grads hooks; it includes both layer4 maps' gradients); the gradient of the audio vectors and the
+    head's internals stay unrounded (kept in fp32 on the GPU).
+    fault (tests only; STEP_FAULTS): "detach_audio" no gradient reaches the audio vectors, "const_norm" the vision
+    map's L2 normalisation is a constant scale in the backward, "pool_spread" the audio pool's gradient is spread as
+    a mean over positions, "ce_sum" CE summed over the batch."""
+    assert fault is None or (fault in STEP_FAULTS and fault != "gan_overwrite"), fault
+    args = args or Args()
+    names, s = _forced_leaves(sd)
+    xin, ain = _bf16_leaf(image), _bf16_leaf(audio)
+    rnd = _bf16_round if round_grads else None
+    vn = _forced_vision_map(s, xin, tape["img"], rnd, fault)
+    an = _forced_audio_vectors(s, ain, tape["aud"], tape["amax"], rnd, fault)
+    A, logits, wA, Pos, Neg = hardway_head(vn, an, args.epsilon, args.epsilon2, tau, args.tri_map, args.Neg)
+    target = torch.zeros(logits.shape[0], dtype=torch.long)
+    loss = cot["scale"] * F.cross_entropy(logits, target, reduction="sum" if fault == "ce_sum" else "mean")
+    for k, out in (("wA", wA), ("A", A), ("Pos", Pos), ("Neg", Neg)):
+        if cot.get(k) is not None:
+            loss = loss + (cot[k].double().reshape(out.shape) * out).sum()
+    loss.backward()
+    grads = {n: _grad_or_zero(s[n]) for n in names}
+    grads["image"], grads["audio"] = _grad_or_zero(xin), _grad_or_zero(ain)
+    return grads
+
+
+def twoview_forced_grads(sd, frames, augmented, spec, tape: dict, loss_weight: float = 0.1, dedup_audio: bool = True,
+                         round_grads: bool = False, fault: str = None, args: Args = None, tau: float = 0.03):
+    """The two-view step's backward (twoview_step's loss: twoview_losses(...)[0] with loss_weight) on a recorded
+    forward.  frames, augmented [b,3,t,H,W], spec [b,1,F,T]; tape["img"] the two views' vision tapes (each view has
+    its own batch statistics); dedup_audio: tape["aud"] = [one tape of the b spectrograms], tape["amax"] = [[b,C]] --
+    the unit vectors are repeated t times ('(b t)' rows) and feed both views' heads, so the audio trunk receives the
+    gradient summed over frames and views; else two tapes of the folded (b t) spectrograms, one per view.  Returns
+    the summed gradients for trainable_names(sd), plus the input gradients "frames", "augmented" (folded,
+    [(b t),3,H,W]) and "audio" (dedup) or "audio1", "audio2".  round_grads as avenet_forced_grads.  fault:
+    avenet_forced_grads' (not "ce_sum"), or "gan_overwrite": view 1's head passes no gradient to the audio vectors
+    (what is left when view 2's audio gradient replaces view 1's where it should add to it)."""
+    assert fault is None or (fault in STEP_FAULTS and fault != "ce_sum"), fault
+    args = args or Args()
+    b, t = frames.shape[0], frames.shape[2]
+    names, s = _forced_leaves(sd)
+    rnd = _bf16_round if round_grads else None
+    xs = [_bf16_leaf(fold_frames(frames)), _bf16_leaf(fold_frames(augmented))]
+    assert len(tape["aud"]) == len(tape["amax"]) == (1 if dedup_audio else 2)
+    ains = [_bf16_leaf(spec)] if dedup_audio else [_bf16_leaf(fold_spec(spec, t)) for _ in range(2)]
+    ans = [_forced_audio_vectors(s, ain, ta, am, rnd, fault) for ain, ta, am in zip(ains, tape["aud"], tape["amax"])]
+    if dedup_audio:
+        ans = [ans[0].repeat_interleave(t, 0)] * 2
+    if fault == "gan_overwrite":
+        ans[0] = ans[0].detach()
+    outs = [hardway_head(_forced_vision_map(s, x, ti, rnd, fault), an, args.epsilon, args.epsilon2, tau,
+                         args.tri_map, args.Neg) for x, ti, an in zip(xs, tape["img"], ans)]
+    twoview_losses(outs[0], outs[1], b, t, loss_weight)[0].backward()
+    grads = {n: _grad_or_zero(s[n]) for n in names}
+    grads["frames"], grads["augmented"] = _grad_or_zero(xs[0]), _grad_or_zero(xs[1])
+    for k, ain in zip(("audio",) if dedup_audio else ("audio1", "audio2"), ains):
+        grads[k] = _grad_or_zero(ain)
+    return grads
