@@ -114,8 +114,11 @@ __global__ __launch_bounds__(kFinThreads) void bn_finalize_kernel(double* __rest
 
 // out = [relu]( x*scale + shift + [residual*rscale + rshift | residual] )
 // The channel block of vector i is i % (C/8); POW2 (C/8 a power of two) takes it as a bit mask.
-// The per-channel constants are re-read every iteration (L1 hits): hoisting them costs enough
-// VGPRs to drop occupancy, which this HBM-bound loop needs more.
+// This grid-stride form re-reads the per-channel constants for every vector: L1 hits, but each one is a
+// vector-memory instruction beside the 1-3 data loads (4-14 of them per 16-byte vector produced), and with one
+// thread per vector there is nothing to hoist them out of.  It is the kernel of a C/8 that does not divide 256
+// (POW2 = false) and of AVT_BN_EW=0; every trunk shape takes the row-walking form below (bn_apply_rw_kernel),
+// which reads the constants once per thread -- measured in profiles/bn_rowwalk_kernel_stats_b128.txt.
 template <bool POW2>
 __device__ __forceinline__ int chan_block(long long i, int cv) {
   return POW2 ? (int)((unsigned)i & (unsigned)(cv - 1)) : (int)(i % cv);
@@ -502,6 +505,417 @@ static int ew_grid(long long nvec) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// Row-walking forms of the elementwise passes (C/8 dividing 256: every trunk shape).  As in bn_bwd_reduce_kernel a
+// thread owns channel chunk tid % (C/8) and walks the rows r0 + k rstep (r0 = tid / (C/8), rstep = 256 / (C/8)) of
+// its block's contiguous row range [blockIdx rpb, +rpb): its 8-channel constants are loaded ONCE, into registers,
+// and the data loads of U rows are issued before the first is consumed; the rows left over go one at a time.  The
+// optional operands are template parameters (no uniform branches in the loop).  Per element the arithmetic is the
+// expression of the grid-stride kernels above in the same order (gamma*invstd is the same product, taken once), so
+// every output bit is the same.
+//
+// AVT_BN_EW (read once; a performance knob, the results are the same bits): 0 = the grid-stride kernels above and
+// the untemplated reduce; 1 (default) = the row-walking forms that measured faster (kBnEwDefault); any other value
+// is a mask of the forms to take, for per-kernel A/B: 2 bn_apply, 4 bn_bwd_apply, 8 bn_bwd_mask_apply,
+// 16 bn_bwd_reduce with its mask constants hoisted.
+enum { kEwFwd = 2, kEwBwd = 4, kEwMaskBwd = 8, kEwReduce = 16 };
+constexpr int kBnEwDefault = kEwFwd | kEwBwd | kEwMaskBwd | kEwReduce;
+static int g_bn_ew = -1;
+static bool bn_ew(int form) {
+  if (g_bn_ew < 0) {
+    const char* e = getenv("AVT_BN_EW");
+    const int v = e ? atoi(e) : 1;
+    g_bn_ew = v == 1 ? kBnEwDefault : (v > 0 ? v : 0);
+  }
+  return (g_bn_ew & form) != 0;
+}
+
+// The grid is sized to the chip, not to the tensor: kBnEwBlocksPerCU blocks per CU (AVT_BN_EW_BPC overrides, for
+// tuning), each with a row range of whole rstep steps and at least one full unrolled iteration.
+constexpr int kBnEwBlocksPerCU = 8;
+struct RowDeal {
+  int nblk;
+  long long rpb;
+};
+static RowDeal rw_deal(long long rows, int C, int U) {
+  static int target = 0;  // blocks per launch: queried once
+  if (target == 0) {
+    int dev = 0, cus = 256;
+    hipDeviceProp_t prop;
+    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess &&
+        prop.multiProcessorCount > 0)
+      cus = prop.multiProcessorCount;
+    const char* e = getenv("AVT_BN_EW_BPC");
+    int bpc = e ? atoi(e) : kBnEwBlocksPerCU;
+    if (bpc < 1) bpc = 1;
+    if (bpc > 64) bpc = 64;
+    target = cus * bpc;
+  }
+  const int rstep = 256 / (C / 8);
+  long long rpb = (rows + target - 1) / target;
+  rpb = ((rpb + rstep - 1) / rstep) * rstep;
+  if (rpb < (long long)U * rstep) rpb = (long long)U * rstep;
+  return {(int)((rows + rpb - 1) / rpb), rpb};
+}
+
+// After a row of an unrolled iteration: the compiler may not move the next row's unpacking and arithmetic up across
+// this point.  Left to itself it widens all U rows to fp32 at once for the sake of instruction-level parallelism
+// these HBM-bound loops have no use for, and takes 160-240 VGPRs (two or three waves per SIMD) for it.
+__device__ __forceinline__ void row_done() { __builtin_amdgcn_sched_barrier(0); }
+
+// the 8 channel constants of a thread's chunk
+__device__ __forceinline__ void load8(float* d, const float* __restrict__ s, int c0) {
+#pragma unroll
+  for (int e = 0; e < 8; ++e) d[e] = s[c0 + e];
+}
+
+// RES: 0 no residual, 1 + residual, 2 + residual*rscale + rshift.  MK: the ReLU mask bits (with RELU).
+template <int RES, bool RELU, bool MK, int U>
+__global__ __launch_bounds__(256) void bn_apply_rw_kernel(const bf16_t* __restrict__ x, const float* __restrict__ scale,
+                                                          const float* __restrict__ shift,
+                                                          const bf16_t* __restrict__ res,
+                                                          const float* __restrict__ rscale,
+                                                          const float* __restrict__ rshift, bf16_t* __restrict__ out,
+                                                          unsigned char* __restrict__ mk, long long rows, int C,
+                                                          long long rpb) {
+  const int cv = C / 8;
+  const int chunk = threadIdx.x % cv, r0 = threadIdx.x / cv, rstep = 256 / cv;
+  const int c0 = chunk * 8;
+  float sc[8], sh[8], rs[8], rh[8];
+  load8(sc, scale, c0);
+  load8(sh, shift, c0);
+  if (RES == 2) {
+    load8(rs, rscale, c0);
+    load8(rh, rshift, c0);
+  }
+  const long long rbeg = blockIdx.x * rpb, rend = min(rows, rbeg + rpb);
+  auto one = [&](const u32x4& xq, const u32x4& rq, size_t o) {
+    float f[8];
+    unpack8(xq, f);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) f[e] = __builtin_fmaf(f[e], sc[e], sh[e]);
+    if (RES) {
+      float r[8];
+      unpack8(rq, r);
+      if (RES == 2) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) f[e] += r[e] * rs[e] + rh[e];
+      } else {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) f[e] += r[e];
+      }
+    }
+    if (RELU) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) f[e] = fmaxf(f[e], 0.f);
+    }
+    const u32x4 v = pack8(f);
+    reinterpret_cast<u32x4*>(out)[o] = v;
+    if (MK) mk[o] = (unsigned char)pos_bits8(v);
+    row_done();
+  };
+  long long r = rbeg + r0;
+  for (; r + (U - 1) * rstep < rend; r += U * rstep) {
+    const size_t o0 = (size_t)r * cv + chunk;  // row r + u rstep is 256 u vectors on (rstep cv = 256)
+    u32x4 xq[U], rq[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const size_t o = o0 + u * 256;
+      xq[u] = reinterpret_cast<const u32x4*>(x)[o];
+      if (RES) rq[u] = reinterpret_cast<const u32x4*>(res)[o];
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) one(xq[u], RES ? rq[u] : xq[u], o0 + u * 256);
+  }
+  for (; r < rend; r += rstep) {
+    const size_t o = (size_t)r * cv + chunk;
+    const u32x4 xq = reinterpret_cast<const u32x4*>(x)[o];
+    one(xq, RES ? reinterpret_cast<const u32x4*>(res)[o] : xq, o);
+  }
+}
+
+template <int RES, bool RELU, bool MK>
+static void bn_apply_rw_launch(const bf16_t* x, const float* scale, const float* shift, const bf16_t* res,
+                               const float* rscale, const float* rshift, bf16_t* out, unsigned char* mk,
+                               long long rows, int C, hipStream_t st) {
+  constexpr int U = 4;
+  const RowDeal d = rw_deal(rows, C, U);
+  hipLaunchKernelGGL((bn_apply_rw_kernel<RES, RELU, MK, U>), dim3(d.nblk), dim3(256), 0, st, x, scale, shift, res,
+                     rscale, rshift, out, mk, rows, C, d.rpb);
+}
+
+// the instantiations avt_bn_apply (MK = false: relu 0 / 1) and avt_bn_apply_mask (MK = true: always ReLU) reach
+template <bool MK>
+static void bn_apply_rw_dispatch(const bf16_t* x, const float* scale, const float* shift, const bf16_t* res,
+                                 const float* rscale, const float* rshift, bf16_t* out, unsigned char* mk,
+                                 long long rows, int C, int relu, hipStream_t st) {
+#define AVT_FWD_RW(RES)                                                                                     \
+  do {                                                                                                      \
+    if (MK || relu)                                                                                         \
+      bn_apply_rw_launch<RES, true, MK>(x, scale, shift, res, rscale, rshift, out, mk, rows, C, st);        \
+    else                                                                                                    \
+      bn_apply_rw_launch<RES, false, false>(x, scale, shift, res, rscale, rshift, out, mk, rows, C, st);    \
+  } while (0)
+  if (!res)
+    AVT_FWD_RW(0);
+  else if (!rscale)
+    AVT_FWD_RW(1);
+  else
+    AVT_FWD_RW(2);
+#undef AVT_FWD_RW
+}
+
+// MASK: 0 none (g is g'), 1 y > 0, 2 fma(xc, mscale, mshift) > 0.  GM: also writes g' to gmask_out.
+template <int MASK, bool GM, int U>
+__global__ __launch_bounds__(256) void bn_bwd_apply_rw_kernel(
+    const bf16_t* __restrict__ g, const bf16_t* __restrict__ y, const float* __restrict__ mscale,
+    const float* __restrict__ mshift, const bf16_t* __restrict__ xc, const float* __restrict__ mean,
+    const float* __restrict__ invstd, const float* __restrict__ gamma, const float* __restrict__ k1,
+    const float* __restrict__ k2, bf16_t* __restrict__ gc, bf16_t* __restrict__ gmask_out, long long rows, int C,
+    long long rpb) {
+  const int cv = C / 8;
+  const int chunk = threadIdx.x % cv, r0 = threadIdx.x / cv, rstep = 256 / cv;
+  const int c0 = chunk * 8;
+  float mu[8], is[8], gi[8], a1[8], a2[8], ms[8], mh[8];
+  load8(mu, mean, c0);
+  load8(is, invstd, c0);
+  load8(gi, gamma, c0);
+  load8(a1, k1, c0);
+  load8(a2, k2, c0);
+#pragma unroll
+  for (int e = 0; e < 8; ++e) gi[e] = gi[e] * is[e];
+  if (MASK == 2) {
+    load8(ms, mscale, c0);
+    load8(mh, mshift, c0);
+  }
+  const long long rbeg = blockIdx.x * rpb, rend = min(rows, rbeg + rpb);
+  auto one = [&](const u32x4& gq, const u32x4& xq, const u32x4& yq, size_t o) {
+    float gg[8], xx[8], v[8];
+    unpack8(gq, gg);
+    unpack8(xq, xx);
+    if (MASK == 1) {
+      float yy[8];
+      unpack8(yq, yy);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) gg[e] = yy[e] > 0.f ? gg[e] : 0.f;
+    } else if (MASK == 2) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) gg[e] = __builtin_fmaf(xx[e], ms[e], mh[e]) > 0.f ? gg[e] : 0.f;
+    }
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const float xh = (xx[e] - mu[e]) * is[e];
+      v[e] = gi[e] * (gg[e] - a1[e] - xh * a2[e]);
+    }
+    reinterpret_cast<u32x4*>(gc)[o] = pack8(v);
+    if (GM) reinterpret_cast<u32x4*>(gmask_out)[o] = pack8(gg);
+    row_done();
+  };
+  long long r = rbeg + r0;
+  for (; r + (U - 1) * rstep < rend; r += U * rstep) {
+    const size_t o0 = (size_t)r * cv + chunk;  // row r + u rstep is 256 u vectors on (rstep cv = 256)
+    u32x4 gq[U], xq[U], yq[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const size_t o = o0 + u * 256;
+      gq[u] = reinterpret_cast<const u32x4*>(g)[o];
+      xq[u] = reinterpret_cast<const u32x4*>(xc)[o];
+      if (MASK == 1) yq[u] = reinterpret_cast<const u32x4*>(y)[o];
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) one(gq[u], xq[u], MASK == 1 ? yq[u] : xq[u], o0 + u * 256);
+  }
+  for (; r < rend; r += rstep) {
+    const size_t o = (size_t)r * cv + chunk;
+    const u32x4 xq = reinterpret_cast<const u32x4*>(xc)[o];
+    one(reinterpret_cast<const u32x4*>(g)[o], xq, MASK == 1 ? reinterpret_cast<const u32x4*>(y)[o] : xq, o);
+  }
+}
+
+// the form of bn_bwd_apply_kernel<true>'s arguments (y, then mscale, decide the mask as in relu_mask8)
+static void bn_bwd_apply_rw_launch(const bf16_t* g, const bf16_t* y, const float* mscale, const float* mshift,
+                                   const bf16_t* xc, const float* mean, const float* invstd, const float* gamma,
+                                   const float* k1, const float* k2, bf16_t* gc, bf16_t* gmask_out, long long rows,
+                                   int C, hipStream_t st) {
+  constexpr int U = 4;
+  const RowDeal d = rw_deal(rows, C, U);
+#define AVT_BWD_RW(MASK, GM)                                                                                        \
+  hipLaunchKernelGGL((bn_bwd_apply_rw_kernel<MASK, GM, U>), dim3(d.nblk), dim3(256), 0, st, g, y, mscale, mshift, xc, \
+                     mean, invstd, gamma, k1, k2, gc, gmask_out, rows, C, d.rpb)
+  if (y) {
+    if (gmask_out) AVT_BWD_RW(1, true); else AVT_BWD_RW(1, false);
+  } else if (mscale) {
+    AVT_BWD_RW(2, false);  // (avt_bn_relu_bwd: no gmask_out)
+  } else {
+    if (gmask_out) AVT_BWD_RW(0, true); else AVT_BWD_RW(0, false);
+  }
+#undef AVT_BWD_RW
+}
+
+// bn_bwd_mask_apply_kernel's row-walking form (MaskApplyArgs::nvec = rows * C/8)
+template <bool TWO, int U>
+__global__ __launch_bounds__(256) void bn_bwd_mask_apply_rw_kernel(MaskApplyArgs a, long long rows, long long rpb) {
+  const int cv = a.C / 8;
+  const int chunk = threadIdx.x % cv, r0 = threadIdx.x / cv, rstep = 256 / cv;
+  const int c0 = chunk * 8;
+  float mu[8], is[8], gi[8], a1[8], a2[8], mu2[8], is2[8], gi2[8], b1[8], b2[8];
+  load8(mu, a.mean, c0);
+  load8(is, a.invstd, c0);
+  load8(gi, a.gamma, c0);
+  load8(a1, a.k1, c0);
+  load8(a2, a.k2, c0);
+#pragma unroll
+  for (int e = 0; e < 8; ++e) gi[e] = gi[e] * is[e];
+  if (TWO) {
+    load8(mu2, a.mean2, c0);
+    load8(is2, a.invstd2, c0);
+    load8(gi2, a.gamma2, c0);
+    load8(b1, a.k1b, c0);
+    load8(b2, a.k2b, c0);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) gi2[e] = gi2[e] * is2[e];
+  }
+  const long long rbeg = blockIdx.x * rpb, rend = min(rows, rbeg + rpb);
+  auto one = [&](const u32x4& gq, unsigned bits, const u32x4& xq, const u32x4& x2q, size_t o) {
+    float gg[8], xx[8], v[8];
+    unpack8(gq, gg);
+    unpack8(xq, xx);
+    mask8(gg, bits);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const float xh = (xx[e] - mu[e]) * is[e];
+      v[e] = gi[e] * (gg[e] - a1[e] - xh * a2[e]);
+    }
+    reinterpret_cast<u32x4*>(a.gc)[o] = pack8(v);
+    if (TWO) {
+      unpack8(x2q, xx);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const float xh = (xx[e] - mu2[e]) * is2[e];
+        v[e] = gi2[e] * (gg[e] - b1[e] - xh * b2[e]);
+      }
+      reinterpret_cast<u32x4*>(a.gc2)[o] = pack8(v);
+    }
+    row_done();
+  };
+  long long r = rbeg + r0;
+  for (; r + (U - 1) * rstep < rend; r += U * rstep) {
+    const size_t o0 = (size_t)r * cv + chunk;  // row r + u rstep is 256 u vectors on (rstep cv = 256)
+    u32x4 gq[U], xq[U], x2q[U];
+    unsigned bq[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const size_t o = o0 + u * 256;
+      gq[u] = reinterpret_cast<const u32x4*>(a.g)[o];
+      xq[u] = reinterpret_cast<const u32x4*>(a.xc)[o];
+      if (TWO) x2q[u] = reinterpret_cast<const u32x4*>(a.xc2)[o];
+      bq[u] = a.mk[o];
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) one(gq[u], bq[u], xq[u], TWO ? x2q[u] : xq[u], o0 + u * 256);
+  }
+  for (; r < rend; r += rstep) {
+    const size_t o = (size_t)r * cv + chunk;
+    const u32x4 xq = reinterpret_cast<const u32x4*>(a.xc)[o];
+    one(reinterpret_cast<const u32x4*>(a.g)[o], a.mk[o], xq, TWO ? reinterpret_cast<const u32x4*>(a.xc2)[o] : xq, o);
+  }
+}
+
+template <bool TWO>
+static void bn_bwd_mask_apply_rw_launch(const MaskApplyArgs& p, long long rows, hipStream_t st) {
+  constexpr int U = TWO ? 2 : 4;  // (TWO holds 80 constants: two rows in flight keep it at four waves per SIMD)
+  const RowDeal d = rw_deal(rows, p.C, U);
+  hipLaunchKernelGGL((bn_bwd_mask_apply_rw_kernel<TWO, U>), dim3(d.nblk), dim3(256), 0, st, p, rows, d.rpb);
+}
+
+// bn_bwd_reduce_kernel with the mask form a template parameter (MASK as bn_bwd_apply_rw_kernel) and the recomputed
+// mask's (mscale, mshift) in registers, not re-read for every row.  Rows, slots and the order of every sum are
+// those of bn_bwd_reduce_kernel: the slots hold the same bits.
+template <int MASK>
+__global__ __launch_bounds__(256) void bn_bwd_reduce_rw_kernel(const bf16_t* __restrict__ g, const bf16_t* __restrict__ y,
+                                                               const float* __restrict__ mscale,
+                                                               const float* __restrict__ mshift,
+                                                               const bf16_t* __restrict__ xc,
+                                                               const float* __restrict__ mean,
+                                                               const float* __restrict__ invstd,
+                                                               double* __restrict__ acc, long long rows, int C,
+                                                               int rows_per_block) {
+  __shared__ float red[2048 * 2];  // [256/(C/8)][C][2] = 4096 floats for any C
+  const int cv = C / 8;
+  const int chunk = threadIdx.x % cv, r0 = threadIdx.x / cv, rstep = 256 / cv;
+  const int c0 = chunk * 8;
+  float mu[8], is[8], ms[8], mh[8], s1[8], s2[8];
+  load8(mu, mean, c0);
+  load8(is, invstd, c0);
+  if (MASK == 2) {
+    load8(ms, mscale, c0);
+    load8(mh, mshift, c0);
+  }
+#pragma unroll
+  for (int e = 0; e < 8; ++e) s1[e] = s2[e] = 0.f;
+  const long long rbeg = (long long)blockIdx.x * rows_per_block;
+  const long long rend = min(rows, rbeg + rows_per_block);
+  auto one = [&](const u32x4& gq, const u32x4& xq, const u32x4& yq) {
+    float gg[8], xx[8];
+    unpack8(gq, gg);
+    unpack8(xq, xx);
+    if (MASK == 1) {
+      float yy[8];
+      unpack8(yq, yy);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) gg[e] = yy[e] > 0.f ? gg[e] : 0.f;
+    } else if (MASK == 2) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) gg[e] = __builtin_fmaf(xx[e], ms[e], mh[e]) > 0.f ? gg[e] : 0.f;
+    }
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      s1[e] += gg[e];
+      // bn_bwd_reduce_kernel's `s2 += g' (x - mu) is` compiles to a product and one fused multiply-add; written
+      // out, because whether the compiler fuses the plain expression depends on the code around it
+      s2[e] = __builtin_fmaf(gg[e] * (xx[e] - mu[e]), is[e], s2[e]);
+    }
+    row_done();
+  };
+  long long r = rbeg + r0;
+  constexpr int U = 4;
+  for (; r + (U - 1) * rstep < rend; r += U * rstep) {
+    const size_t o0 = (size_t)r * cv + chunk;  // row r + u rstep is 256 u vectors on (rstep cv = 256)
+    u32x4 gq[U], xq[U], yq[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const size_t o = o0 + u * 256;
+      gq[u] = reinterpret_cast<const u32x4*>(g)[o];
+      xq[u] = reinterpret_cast<const u32x4*>(xc)[o];
+      if (MASK == 1) yq[u] = reinterpret_cast<const u32x4*>(y)[o];
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) one(gq[u], xq[u], MASK == 1 ? yq[u] : xq[u]);
+  }
+  for (; r < rend; r += rstep) {
+    const size_t o = (size_t)r * cv + chunk;
+    const u32x4 xq = reinterpret_cast<const u32x4*>(xc)[o];
+    one(reinterpret_cast<const u32x4*>(g)[o], xq, MASK == 1 ? reinterpret_cast<const u32x4*>(y)[o] : xq);
+  }
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    red[(r0 * C + c0 + e) * 2] = s1[e];
+    red[(r0 * C + c0 + e) * 2 + 1] = s2[e];
+  }
+  __syncthreads();
+  bn_write_header(acc, gridDim.x, 0);
+  double* slot = bn_bwd_slots(acc, C) + (size_t)blockIdx.x * C * 2;  // this block's own slot
+  for (int c = threadIdx.x; c < C; c += blockDim.x) {
+    float a = 0.f, b = 0.f;
+    for (int k = 0; k < rstep; ++k) {
+      a += red[(k * C + c) * 2];
+      b += red[(k * C + c) * 2 + 1];
+    }
+    slot[2 * c] = (double)a;
+    slot[2 * c + 1] = (double)b;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
 // Stem: bn1 -> relu -> MaxPool2d(3,2,1) (models/base_models.py:200-203) without materialising the
 // full-resolution activation h0 = relu(bn(c0)), the largest tensor of either trunk.
 //   fwd : one thread per (pooled pixel, 8 channels) evaluates h0 on its 3x3 window exactly as
@@ -722,8 +1136,18 @@ static void bn_bwd_reduce_launch(const bf16_t* g, const bf16_t* y, const float* 
   rpb = ((rpb + rstep - 1) / rstep) * rstep;
   if (rpb < rstep) rpb = rstep;
   const int nblk = (int)((rows + rpb - 1) / rpb);
-  hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3(nblk), dim3(256), 0, st, g, y, mscale, mshift, xc, mean, invstd, acc,
-                     rows, C, (int)rpb);
+  if (!bn_ew(kEwReduce))
+    hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3(nblk), dim3(256), 0, st, g, y, mscale, mshift, xc, mean, invstd, acc,
+                       rows, C, (int)rpb);
+  else if (y)
+    hipLaunchKernelGGL(bn_bwd_reduce_rw_kernel<1>, dim3(nblk), dim3(256), 0, st, g, y, mscale, mshift, xc, mean, invstd,
+                       acc, rows, C, (int)rpb);
+  else if (mscale)
+    hipLaunchKernelGGL(bn_bwd_reduce_rw_kernel<2>, dim3(nblk), dim3(256), 0, st, g, y, mscale, mshift, xc, mean, invstd,
+                       acc, rows, C, (int)rpb);
+  else
+    hipLaunchKernelGGL(bn_bwd_reduce_rw_kernel<0>, dim3(nblk), dim3(256), 0, st, g, y, mscale, mshift, xc, mean, invstd,
+                       acc, rows, C, (int)rpb);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -944,7 +1368,10 @@ extern "C" int avt_bn_apply(const void* x, const float* scale, const float* shif
   const long long nvec = rows * C / 8;
   if (nvec == 0 || diag_skip(16, (hipStream_t)stream)) return AVT_OK;
   const int grid = ew_grid(nvec);
-  if (256 % (C / 8) == 0)
+  if (256 % (C / 8) == 0 && bn_ew(kEwFwd))
+    bn_apply_rw_dispatch<false>((const bf16_t*)x, scale, shift, (const bf16_t*)residual, rscale, rshift, (bf16_t*)out,
+                                nullptr, rows, C, relu, (hipStream_t)stream);
+  else if (256 % (C / 8) == 0)
     hipLaunchKernelGGL(bn_apply_kernel<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, scale,
                        shift, (const bf16_t*)residual, rscale, rshift, (bf16_t*)out, nullptr, nvec, C, relu);
   else
@@ -961,9 +1388,13 @@ extern "C" int avt_bn_apply_mask(const void* x, const float* scale, const float*
   AVT_REQUIRE((rscale == nullptr) == (rshift == nullptr), "bn_apply_mask: rscale/rshift must be both set or both null");
   const long long nvec = rows * C / 8;
   if (nvec == 0 || diag_skip(16, (hipStream_t)stream)) return AVT_OK;
-  hipLaunchKernelGGL(bn_apply_kernel<true>, dim3(ew_grid(nvec)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x,
-                     scale, shift, (const bf16_t*)residual, rscale, rshift, (bf16_t*)out, (unsigned char*)mask, nvec, C,
-                     1);
+  if (bn_ew(kEwFwd))
+    bn_apply_rw_dispatch<true>((const bf16_t*)x, scale, shift, (const bf16_t*)residual, rscale, rshift, (bf16_t*)out,
+                               (unsigned char*)mask, rows, C, 1, (hipStream_t)stream);
+  else
+    hipLaunchKernelGGL(bn_apply_kernel<true>, dim3(ew_grid(nvec)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x,
+                       scale, shift, (const bf16_t*)residual, rscale, rshift, (bf16_t*)out, (unsigned char*)mask, nvec,
+                       C, 1);
   return check_launch("bn_apply_mask");
 }
 
@@ -1030,14 +1461,20 @@ extern "C" int avt_bn_bwd_mask(const void* g, const void* mask, const avt_bn_bwd
     p.k1b = k1b;
     p.k2b = k1b + C;
     p.gc2 = (bf16_t*)t2->gc;
-    hipLaunchKernelGGL(bn_bwd_mask_apply_kernel<true>, dim3(ew_grid(p.nvec)), dim3(256), 0, st, p);
+    if (bn_ew(kEwMaskBwd))
+      bn_bwd_mask_apply_rw_launch<true>(p, rows, st);
+    else
+      hipLaunchKernelGGL(bn_bwd_mask_apply_kernel<true>, dim3(ew_grid(p.nvec)), dim3(256), 0, st, p);
   } else {
     if (!diag_skip(8, st)) hipLaunchKernelGGL(bn_bwd_mask_reduce_kernel<false>, dim3(nblk), dim3(256), 0, st, a);
     if (diag_skip(64, st)) hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + kFinCB - 1) / kFinCB), dim3(kFinThreads), 0, st, acc, C, inv_rows, t1->dgamma,
                        t1->dbeta, k1, k1 + C);
     if (!diag_skip(2, st)) hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + kFinCB - 1) / kFinCB), dim3(kFinThreads), 0, st, acc, C, inv_rows, t1->dgamma,
                        t1->dbeta, k1, k1 + C);
-    hipLaunchKernelGGL(bn_bwd_mask_apply_kernel<false>, dim3(ew_grid(p.nvec)), dim3(256), 0, st, p);
+    if (bn_ew(kEwMaskBwd))
+      bn_bwd_mask_apply_rw_launch<false>(p, rows, st);
+    else
+      hipLaunchKernelGGL(bn_bwd_mask_apply_kernel<false>, dim3(ew_grid(p.nvec)), dim3(256), 0, st, p);
   }
   return check_launch("bn_bwd_mask");
 }
@@ -1067,9 +1504,14 @@ extern "C" int avt_bn_bwd(const void* g, const void* y, const void* xc, const fl
   if (!diag_skip(2, st)) hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + kFinCB - 1) / kFinCB), dim3(kFinThreads), 0, st, acc, C, 1.0 / (double)rows,
                      dgamma, dbeta, k1, k2);
   const long long nvec = rows * C / 8;
-  hipLaunchKernelGGL(bn_bwd_apply_kernel<true>, dim3(ew_grid(nvec)), dim3(256), 0, st, (const bf16_t*)g, (const bf16_t*)y,
-                     nullptr, nullptr, (const bf16_t*)xc, mean, invstd, gamma, k1, k2, (bf16_t*)gc,
-                     (bf16_t*)gmask_out, nvec, C);
+  if (bn_ew(kEwBwd))
+    bn_bwd_apply_rw_launch((const bf16_t*)g, (const bf16_t*)y,
+                           nullptr, nullptr, (const bf16_t*)xc, mean, invstd, gamma, k1, k2, (bf16_t*)gc,
+                           (bf16_t*)gmask_out, rows, C, st);
+  else
+    hipLaunchKernelGGL(bn_bwd_apply_kernel<true>, dim3(ew_grid(nvec)), dim3(256), 0, st, (const bf16_t*)g, (const bf16_t*)y,
+                       nullptr, nullptr, (const bf16_t*)xc, mean, invstd, gamma, k1, k2, (bf16_t*)gc,
+                       (bf16_t*)gmask_out, nvec, C);
   return check_launch("bn_bwd");
 }
 
@@ -1092,8 +1534,12 @@ extern "C" int avt_bn_bwd_premasked(const void* gm, const void* xc, const float*
   if (!diag_skip(2, st)) hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + kFinCB - 1) / kFinCB), dim3(kFinThreads), 0, st, acc, C, 1.0 / (double)rows,
                      dgamma, dbeta, k1, k2);
   const long long nvec = rows * C / 8;
-  hipLaunchKernelGGL(bn_bwd_apply_kernel<true>, dim3(ew_grid(nvec)), dim3(256), 0, st, (const bf16_t*)gm, nullptr,
-                     nullptr, nullptr, (const bf16_t*)xc, mean, invstd, gamma, k1, k2, (bf16_t*)gc, nullptr, nvec, C);
+  if (bn_ew(kEwBwd))
+    bn_bwd_apply_rw_launch((const bf16_t*)gm, nullptr,
+                           nullptr, nullptr, (const bf16_t*)xc, mean, invstd, gamma, k1, k2, (bf16_t*)gc, nullptr, rows, C, st);
+  else
+    hipLaunchKernelGGL(bn_bwd_apply_kernel<true>, dim3(ew_grid(nvec)), dim3(256), 0, st, (const bf16_t*)gm, nullptr,
+                       nullptr, nullptr, (const bf16_t*)xc, mean, invstd, gamma, k1, k2, (bf16_t*)gc, nullptr, nvec, C);
   return check_launch("bn_bwd_premasked");
 }
 
@@ -1117,8 +1563,12 @@ extern "C" int avt_bn_relu_bwd(const void* g, const void* xc, const float* scale
   if (!diag_skip(2, st)) hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + kFinCB - 1) / kFinCB), dim3(kFinThreads), 0, st, acc, C, 1.0 / (double)rows,
                      dgamma, dbeta, k1, k2);
   const long long nvec = rows * C / 8;
-  hipLaunchKernelGGL(bn_bwd_apply_kernel<true>, dim3(ew_grid(nvec)), dim3(256), 0, st, (const bf16_t*)g, nullptr, scale,
-                     shift, (const bf16_t*)xc, mean, invstd, gamma, k1, k2, (bf16_t*)gc, nullptr, nvec, C);
+  if (bn_ew(kEwBwd))
+    bn_bwd_apply_rw_launch((const bf16_t*)g, nullptr, scale,
+                           shift, (const bf16_t*)xc, mean, invstd, gamma, k1, k2, (bf16_t*)gc, nullptr, rows, C, st);
+  else
+    hipLaunchKernelGGL(bn_bwd_apply_kernel<true>, dim3(ew_grid(nvec)), dim3(256), 0, st, (const bf16_t*)g, nullptr, scale,
+                       shift, (const bf16_t*)xc, mean, invstd, gamma, k1, k2, (bf16_t*)gc, nullptr, nvec, C);
   return check_launch("bn_relu_bwd");
 }
 
