@@ -577,7 +577,8 @@ class _FullModelFunction(torch.autograd.Function):
 
 class FullModel(nn.Module):
     """model.py:17-36 on libavt: R3D-18 ``vidnet`` (forward only; its layer4 is detached as the
-    reference's forward hook does), audio ResNet-18 ``audnet``, AdaptiveMaxPool2d + normalize,
+    reference's forward hook does -- unless ``enable_video_backward()`` opted in to training it end to end),
+    audio ResNet-18 ``audnet``, AdaptiveMaxPool2d + normalize,
     HardWayAttention.  ``forward(audio, video) -> (A, logits)`` with audio either the folded
     repeated spectrogram [b*t,1,F,T] (the reference call, train_3D.py:128-131) or one spectrogram
     per clip [b,1,F,T] (de-duplicated audio trunk, exact; tube.py)."""
@@ -595,6 +596,7 @@ class FullModel(nn.Module):
         self._flat = FlatStore(self, tube_trainable)
         self._engine = None
         self._avt_folded = False  # enable_folded_inference(): BatchNorm folded into the convs for eval calls
+        self._avt_video_backward = False  # enable_video_backward(): the video trunk trained end to end
         self.audnet._adopt(self, "audnet.")
         self.vidnet._adopt(self, "vidnet.")
 
@@ -611,6 +613,29 @@ class FullModel(nn.Module):
         model that never calls this.  ``model.vidnet(video)`` and ``model.audnet(x)`` follow this flag.  Idempotent;
         returns self."""
         self._avt_folded = True
+        return self
+
+    def enable_video_backward(self):
+        """Opt in to training the video trunk end to end: the layer4 map the head reads stays attached (the reference's
+        hook stores ``output.detach()``, model.py:14, so by default no gradient reaches ``vidnet``).  After the call, in
+        train mode, every ``vidnet`` parameter the layer4 map depends on -- ``conv1``, ``bn1``, ``layer1..4.*`` with
+        their downsample convs and BNs -- receives its gradient from the loss (through ``logits`` and the returned
+        ``A``), on the drop-in autograd path (``loss.backward()``; ``torch.optim.Adam`` / ``avt_amd.optim.Adam`` on
+        ``model.parameters()``) and in ``train.HardWayTrainStep(model)``, eager or captured, for both audio forms.
+        ``vidnet.fc.*`` sits behind the tap: its ``.grad`` stays None and no optimizer touches it; the audnet rules
+        are unchanged.  The flat store is rebuilt from the current parameter values on the current device (call this
+        before building an optimizer or a train step over the model); ``state_dict`` keys, shapes and values do not
+        change.  An eval-mode model still computes no gradient, the folded inference forward is untouched, no gradient
+        of the video tensor itself is computed (a video that requires grad raises), and a model that never calls this
+        runs exactly as before.  Idempotent; returns self."""
+        if not getattr(self, "_avt_video_backward", False):
+            from .tube import tube_trainable_e2e
+
+            self._avt_video_backward = True
+            self._flat = FlatStore(self, tube_trainable_e2e)  # from the current parameter values (and device)
+            self._engine = None
+            self.audnet._avt_engine = None
+            self.vidnet._avt_engine = None
         return self
 
     def invalidate_folded(self):
@@ -646,7 +671,7 @@ class FullModel(nn.Module):
         if self._engine is None:
             from .tube import TubeEngine
 
-            self._engine = TubeEngine(self._flat)
+            self._engine = TubeEngine(self._flat, video_backward=getattr(self, "_avt_video_backward", False))
         return self._engine
 
     def forward(self, audio, video):
@@ -655,6 +680,10 @@ class FullModel(nn.Module):
         n_train = sum(1 for n in self._flat.pnames if self._flat.trainable(n))
         train_params = [named[n] for n in self._flat.pnames[:n_train]]
         if torch.is_grad_enabled() and self.training and any(p.requires_grad for p in train_params):
+            if eng.video_backward and video.requires_grad:
+                raise NotImplementedError("avt: FullModel computes no gradient of the video tensor itself; pass a video "
+                                          "that does not require grad (enable_video_backward() trains the trunk's "
+                                          "parameters)")
             return _FullModelFunction.apply(eng, True, audio, video, *train_params)
         if not self.training and getattr(self, "_avt_folded", False):
             out, _ = eng.forward_folded(audio, video)

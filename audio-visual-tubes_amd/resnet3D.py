@@ -151,10 +151,12 @@ class ResNet(nn.Module):
         eval_grad=True: grad-mode calls of an eval-mode trunk are differentiated too, BatchNorm by its
         running-statistics rule (no running statistic or num_batches_tracked changes).  A later call can only widen
         the opt-in, and rebuilds nothing once the trunk is trainable.  Raises on a trunk adopted by a FullModel (the
-        reference detaches that trunk, model.py:14; the tube step computes no video gradients)."""
+        reference detaches that trunk, model.py:14; ``FullModel.enable_video_backward()`` is the opt-in that trains
+        it, from the model's loss)."""
         if self._avt_parent is not None:
-            raise RuntimeError("avt: enable_backward() is for a standalone R3D trunk; FullModel.vidnet is detached "
-                               "(model.py:14) and stays forward-only")
+            raise RuntimeError("avt: enable_backward() is for a standalone R3D trunk; to train FullModel.vidnet end to "
+                               "end call FullModel.enable_video_backward() on the owning model (the trunk's gradients "
+                               "then come from the model's loss)")
         if not self._avt_backward:
             self._avt_backward = True
             if self._own_flat is not None:  # rebuild from the current parameter values (and device)
@@ -184,8 +186,9 @@ class ResNet(nn.Module):
                                       "tensor that does not require grad (a standalone trunk computes it after "
                                       "net.enable_backward(input_grad=True))")
         if need_grad and not (self._avt_backward and self._avt_parent is None):
-            raise NotImplementedError("avt: the R3D trunk is forward-only in this build (FullModel detaches it); "
-                                      "call it under torch.no_grad() or with requires_grad_(False) parameters.  A "
+            raise NotImplementedError("avt: the R3D trunk called on its own is forward-only inside a FullModel (the "
+                                      "model trains it from its loss after FullModel.enable_video_backward()); call "
+                                      "it under torch.no_grad() or with requires_grad_(False) parameters.  A "
                                       "standalone trunk becomes trainable after net.enable_backward().")
         if need_grad and not self.training and not self._avt_eval_grad:
             raise NotImplementedError("avt: gradients through an eval-mode trunk are not computed (train-mode "

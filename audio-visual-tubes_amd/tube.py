@@ -8,6 +8,9 @@ Restates model.py:17-60 and the train_3D.py step (126-138):
   video [b,3,t,H,W] --vidnet (R3D-18, no max-pool)--> layer4 [b,512,t,h,w] (forward hook,
       DETACHED: model.py:12-15, 34) --normalize, '(b t) c h w'--> HardWayAttention -> (A, logits)
   CE(logits, 0) -> backward into audnet only -> Adam.
+  Opt-in (FullModel.enable_video_backward): the layer4 map stays attached -- the head backward also yields
+  gv, R3DTrunk.backward fills the vidnet gradients (all but vidnet.fc, which sits behind the tap) in the same flat
+  buffer, on the current stream while the audio trunk's backward runs on the second one.
 
 Device data flow (NHWC / NDHWC bf16 activations, fp32 statistics):
   video fp32 NCDHW --avt_video_stem_im2col--> [b,t,H,W,32] (7 temporal taps folded into channels)
@@ -51,6 +54,15 @@ def tube_trainable(name: str) -> bool:
     if ".fc." in name or name.endswith("conv1_flow.weight") or name == "audnet.conv1.weight":
         return False
     return True
+
+
+def tube_trainable_e2e(name: str) -> bool:
+    """tube_trainable plus the video trunk up to the layer4 tap (FullModel.enable_video_backward): conv1, bn1 and
+    layer1..4 with their downsamples.  vidnet.fc sits behind the tap (the discarded `_` of model.py:33) and never
+    receives a gradient, so it stays outside the trainable segment: the flat Adam never touches it."""
+    if name.startswith("vidnet."):
+        return not name.startswith("vidnet.fc.")
+    return tube_trainable(name)
 
 
 @dataclass
@@ -316,7 +328,9 @@ class R3DTrunk:
                          2.0 * (gy.numel() + wt.numel() + gx.numel()))
         return gx
 
-    def backward(self, tape, g: torch.Tensor, store, training: bool = True, gvideo=None) -> None:
+    HI_BLOCK = 4  # index of layer3.0 in self.blocks (the gradient buckets' boundary, as Trunk.HI_BLOCK)
+
+    def backward(self, tape, g: torch.Tensor, store, training: bool = True, gvideo=None, on_boundary=None) -> None:
         """g bf16 [b*T, h, w, 512] = d(loss)/d(layer4 map) -> the trunk's parameter gradients, accumulated into
         store.grad(name) (zeroed by the caller).  Blocks in reverse, unfused (autograd through BasicBlock.forward,
         resnet3D.py:45-61): bn2 (+ downsample.1) backward, conv2 wgrad + dgrad, bn1+relu backward, conv1 wgrad + dgrad
@@ -324,9 +338,18 @@ class R3DTrunk:
         the 1x1x1 downsample), then the stem's max-pool / BN+ReLU backward and its folded weight gradient.
         training=False: the tape of an eval-mode forward, every BatchNorm backward by the running-statistics rule
         (avt_bn_eval_bwd; a first block's bn2 + downsample.1 in one pass).  gvideo (fp32 [b,3,t,H,W], optional)
-        receives the video's gradient (avt_video_stem_dgrad on the stem's gc0)."""
+        receives the video's gradient (avt_video_stem_dgrad on the stem's gc0).  on_boundary(prefix + "hi") is called
+        once layer4 and layer3 are done (as Trunk.backward: those gradients are final there)."""
+        g = self.backward_blocks(tape, g, store, self.HI_BLOCK, len(self.blocks), training)
+        if on_boundary is not None:
+            on_boundary(self.prefix + "hi")
+        g = self.backward_blocks(tape, g, store, 0, self.HI_BLOCK, training)
+        self.backward_stem(tape, g, store, training, gvideo)
+
+    def backward_blocks(self, tape, g: torch.Tensor, store, lo: int, hi: int, training: bool = True):
+        """backward's blocks hi-1 .. lo; returns the gradient of block lo's input."""
         b = tape["b"]
-        for blk, tb in zip(reversed(self.blocks), reversed(tape["blocks"])):
+        for blk, tb in zip(reversed(self.blocks[lo:hi]), reversed(tape["blocks"][lo:hi])):
             T, H, W, Ho, Wo = tb["dims"]
             gm = gcd = None
             if training or blk["down"] is None:
@@ -352,6 +375,11 @@ class R3DTrunk:
                      dn.k, dn.k, dn.stride, dn.pad, stream_ptr())
             else:
                 g = self._dgrad(gc1, b, T, H, W, blk["conv1"], store, add=gm)
+        return g
+
+    def backward_stem(self, tape, g: torch.Tensor, store, training: bool = True, gvideo=None) -> None:
+        """backward's tail: the stem's max-pool / BN+ReLU backward, its folded weight gradient, the video's gradient."""
+        b = tape["b"]
         T, H, W = tape["dims0"]
         if self.max_pool:  # resnet3D.py:200-201
             gp = torch.empty_like(tape["h0"])
@@ -475,9 +503,15 @@ class _TubeStore(_EngineStore):
 
 
 class TubeEngine(AVEngine):
-    """R3D-18 + audio ResNet-18 + HardWayAttention head on one device."""
+    """R3D-18 + audio ResNet-18 + HardWayAttention head on one device.  video_backward (a FullModel after
+    ``enable_video_backward()``; flat's trainable segment then holds the vidnet parameters): the Conv3d dgrad operands
+    are packed with the forward ones, a train-mode forward keeps the video trunk's tape, the head backward also
+    produces gv, and ``backward`` runs R3DTrunk.backward on the current stream next to the audio trunk's on the second
+    one."""
 
-    def __init__(self, flat: FlatStore):
+    def __init__(self, flat: FlatStore, video_backward: bool = False):
+        self.video_backward = self.with_backward = bool(video_backward)  # (with_backward: read by _alloc_packs3d)
+        self.packs3d_t: Dict[str, torch.Tensor] = {}
         super().__init__(flat, 0.65, 0.4, 0.03, True, True)  # HardWayAttention's fixed constants (model.py:41-44)
         self.store = _TubeStore(self)
 
@@ -517,21 +551,32 @@ class TubeEngine(AVEngine):
         return B, rep
 
     def forward(self, audio: torch.Tensor, video: torch.Tensor, training: bool, with_ce: bool = False,
-                ce_scale: float = 1.0):
+                ce_scale: float = 1.0, vision_pre=None):
         """audio: [b*t,1,F,T] (folded repeated spectrogram, model.py API) or [b,1,F,T] (one per clip,
-        de-duplicated); video: [b,3,t,H,W].  Returns ({'A', 'logits'[, 'loss', 'dlogits']}, tape)."""
+        de-duplicated); video: [b,3,t,H,W].  Returns ({'A', 'logits'[, 'loss', 'dlogits']}, tape).  vision_pre():
+        launches issued ahead of the trunks (the data-parallel step's Adam prep and gradient zeroing, train.py).
+        video_backward: a train-mode tape also holds the video trunk's (tape["vid"])."""
         B, rep = self._check_tube_inputs(audio, video)
         self.pack_weights()
         if training:
             self.flat.nbt.add_(1)
+        if vision_pre is not None:
+            vision_pre()
         xa = self._to_nhwc(audio, 1)
         self.aud.bn_rep = rep
         try:
             a, tape_a = self.aud.forward(xa, self.store, training)
         finally:
             self.aud.bn_rep = 1
-        v = self.vid.forward(video, self.store, training)
-        return self._tube_head(a, tape_a, v, B, rep, training, with_ce, ce_scale)
+        tape_v = None
+        if training and self.video_backward:
+            v, tape_v = self.vid.forward(video, self.store, training, tape=True)
+        else:
+            v = self.vid.forward(video, self.store, training)
+        out, tape = self._tube_head(a, tape_a, v, B, rep, training, with_ce, ce_scale)
+        if tape is not None:
+            tape["vid"] = tape_v
+        return out, tape
 
     def forward_folded(self, audio: torch.Tensor, video: torch.Tensor):
         """forward(training=False) on the folded inference path (FullModel.enable_folded_inference): the audio trunk
@@ -596,11 +641,14 @@ class TubeEngine(AVEngine):
 
     # ----------------------------------------------------------------------------- backward
     def backward_order(self):
-        return [self.aud]
+        return [self.vid, self.aud] if self.video_backward else [self.aud]
 
     def backward(self, tape, dlogits: Optional[torch.Tensor], gflat: torch.Tensor, on_boundary=None, dA=None):
         """Accumulate d(loss)/d(audnet params) into gflat[:n_train] (caller zeroes it).  dA (optional):
-        upstream gradient of the returned A map (model.py:60)."""
+        upstream gradient of the returned A map (model.py:60).  video_backward: the vidnet parameters' too
+        (_backward_e2e)."""
+        if self.video_backward:
+            return self._backward_e2e(tape, dlogits, gflat, on_boundary, dA)
         B, Pn, C, rep, Ba = tape["B"], tape["P"], tape["C"], tape["rep"], tape["Ba"]
         dev = tape["A0"].device
         f32 = dict(device=dev, dtype=torch.float32)
@@ -628,6 +676,58 @@ class TubeEngine(AVEngine):
         finally:
             self.store.grads = None
 
+    def _backward_e2e(self, tape, dlogits, gflat, on_boundary, dA):
+        """backward with the video trunk attached: the head backward with gv (AVEngine.head_backward: dvh fp32
+        [B][P][C], gv bf16 '(b t) h w c' -- the layout R3DTrunk.backward reads), then the two trunks' backwards, which
+        share nothing but the read-only tape: the video trunk's on the current stream, the audio trunk's (the row sum
+        over each clip's frames, the pool/normalise backward, Trunk.backward) on the second one, forked behind the head
+        and joined before returning -- two branches, as AVEngine's.  on_boundary (the data-parallel schedule): both
+        trunks' layer4+layer3, a join and on_boundary(("vidnet.hi", "audnet.hi")), then the rest of both, a join and
+        on_boundary(("vidnet.lo", "audnet.lo")), on the current stream as AVEngine.backward calls it.  No atomics; each
+        wgrad sums its own slabs in split order, so the gradient bits do not depend on the streams."""
+        if tape.get("vid") is None:
+            raise RuntimeError("avt: this tape holds no video-trunk tape (a forward of an engine without video_backward)")
+        B, C, rep, Ba = tape["B"], tape["C"], tape["rep"], tape["Ba"]
+        gv, gan = self.head_backward(tape, dlogits, dA=dA)
+        a, aud, vid, ta, tv = tape["a"], self.aud, self.vid, tape["aud"], tape["vid"]
+        hi = aud.HI_BLOCK
+        assert hi == vid.HI_BLOCK
+
+        def audio_hi():
+            if rep > 1:
+                gan_a = torch.empty(Ba, C, device=gan.device, dtype=torch.float32)
+                call("avt_sum_rep_rows_f32", P(gan), P(gan_a), Ba, rep, C, stream_ptr())
+            else:
+                gan_a = gan
+            ga = torch.empty_like(a)
+            call("avt_audio_pool_norm_bwd", P(gan_a), P(tape["an_a"]), P(tape["amax"]), P(tape["anorm"]), P(ga), Ba,
+                 a.shape[1] * a.shape[2], C, stream_ptr())
+            return aud.backward_blocks(ta, ga, self.store, hi, len(aud.blocks))
+
+        def audio_lo(g, pm):
+            g, _ = aud.backward_blocks(ta, g, self.store, 0, hi, pm)
+            aud.backward_stem(ta, g, self.store)
+
+        self.store.grads = self.flat.grad_views(gflat)
+        try:
+            with self._branch():
+                ga, pm = audio_hi()
+                if on_boundary is None:
+                    audio_lo(ga, pm)
+            gv = vid.backward_blocks(tv, gv, self.store, hi, len(vid.blocks))
+            if on_boundary is not None:
+                self._join()
+                on_boundary((vid.prefix + "hi", aud.prefix + "hi"))
+                with self._branch():
+                    audio_lo(ga, pm)
+            gv = vid.backward_blocks(tv, gv, self.store, 0, hi)
+            vid.backward_stem(tv, gv, self.store)
+            self._join()
+            if on_boundary is not None:
+                on_boundary((vid.prefix + "lo", aud.prefix + "lo"))
+        finally:
+            self.store.grads = None
+
 
 class R3DEngine(AVEngine):
     """The R3D-18 trunk called on its own -- ``FullModel.vidnet(video)`` or a standalone
@@ -635,7 +735,8 @@ class R3DEngine(AVEngine):
     layer4 on libavt as inside FullModel (R3DTrunk), then AdaptiveAvgPool3d((1,1,1)) + fc on the pooled
     fp32 features.  with_backward (a standalone module after ``enable_backward()``): the dgrad operands are packed
     too, ``forward(..., tape=True)`` keeps the backward's tape and ``backward`` fills the flat gradient of every
-    vidnet parameter; inside FullModel the trunk stays forward-only (the reference detaches it, model.py:14)."""
+    vidnet parameter; ``FullModel.vidnet(video)`` called on its own stays forward-only (the reference detaches the trunk,
+    model.py:14; FullModel.enable_video_backward trains it from the model's loss, through TubeEngine)."""
 
     def __init__(self, flat: FlatStore, prefix: str, max_pool: bool = False, with_backward: bool = False):
         self._prefix = prefix
