@@ -16,13 +16,14 @@ CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_PATH = os.path.join(PKG_DIR, "libavt.so")
 # A/B measurement only: load another in-tree build of the same ABI (e.g. libavt_base.so)
 LOAD_PATH = os.environ.get("AVT_LIB_PATH", LIB_PATH)
-SOURCES = ["conv_gemm.hip", "bn.hip", "pool.hip", "head.hip", "misc.hip", "tube.hip", "conv3d_bwd.hip", "eval.hip", "audio.hip", "frames.hip"]
+SOURCES = ["conv_gemm.hip", "bn.hip", "pool.hip", "head.hip", "misc.hip", "tube.hip", "conv3d_bwd.hip", "eval.hip", "audio.hip", "frames.hip", "render.hip"]
 
 _P = ctypes.c_void_p
 _I = ctypes.c_int
 _L = ctypes.c_longlong
 _F = ctypes.c_float
 _Z = ctypes.c_size_t
+_D = ctypes.c_double
 
 class DgradBnEpi(ctypes.Structure):
     """avt_dgrad_bn_epi (include/avt.h): the BatchNorm-backward epilogue of avt_conv2d_dgrad_bn."""
@@ -158,6 +159,8 @@ SIGNATURES = {
     "avt_flip_l1_loss": (_I, [_P, _P, _L, _I, _P, _P, _P, _P, _P]),
     "avt_localize_ciou": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "avt_pair_ciou": (_I, [_P, _I, _I, _P, _P]),
+    "avt_heatmap_upsample": (_I, [_P, _I, _I, _I, _I, _I, _P, _P]),
+    "avt_render_overlay": (_I, [_P, _I, _I, _I, _P, _F, _D, _P, _F, _D, _F, _P, _P, _P]),
     "avt_spectrogram_segments": (_I, [_L, _I]),
     "avt_spectrogram": (_I, [_P, _I, _L, _I, _F, _P, _P]),
     "avt_frames_transform": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _P]),
@@ -256,6 +259,11 @@ def lib() -> ctypes.CDLL:
             if LOAD_PATH == LIB_PATH and _recorded_hash() != source_hash():
                 raise RuntimeError(f"{LIB_PATH} was not built from the current csrc/ sources (hash record "
                                    f"{HASH_PATH} differs); run __graft_entry__.build()")
+            # torch first: its wheel carries its own libamdhip64 (same soname), which libavt then shares.  Loaded the
+            # other way round -- build() and smoke() in one fresh process -- the process holds two HIP runtimes and
+            # the library's own finds no device.
+            import torch  # noqa: F401
+
             h = ctypes.CDLL(LOAD_PATH)
             for name, (res, args) in SIGNATURES.items():
                 if LOAD_PATH != LIB_PATH and not hasattr(h, name):

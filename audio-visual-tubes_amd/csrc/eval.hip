@@ -15,6 +15,7 @@
 // preserving integer image of the fp32 pred values (4 passes of 8 bits, the map recomputed per
 // pass: 50176 values do not fit in LDS); the cIoU sums are fp64 like numpy's.
 #include "avt_common.h"
+#include "exact_fp.h"
 
 namespace avt {
 
@@ -34,9 +35,9 @@ struct EvalTabs {
 // cv2 resize (INTER_LINEAR) source index / weights of destination coordinate d
 __device__ __forceinline__ void lin_coef(int d, int src, int dst, int& s, float& a0, float& a1) {
   // cv2: fx = (float)((dx + 0.5) * scale_x - 0.5) with scale_x = (double)src / dst
-  float f = (float)(((double)d + 0.5) * ((double)src / (double)dst) - 0.5);
+  float f = (float)sub_rn(mul_rn((double)d + 0.5, (double)src / (double)dst), 0.5);
   int i = (int)floorf(f);
-  f = __fsub_rn(f, (float)i);
+  f = sub_rn(f, (float)i);
   if (i < 0) {
     f = 0.f;
     i = 0;
@@ -46,25 +47,25 @@ __device__ __forceinline__ void lin_coef(int d, int src, int dst, int& s, float&
     i = src - 1;
   }
   s = i;
-  a0 = __fsub_rn(1.f, f);
+  a0 = sub_rn(1.f, f);
   a1 = f;
 }
 
 __device__ __forceinline__ float resized(const float* __restrict__ m, int h, int w, const EvalTabs& tb, int y, int x) {
   const int sy = tb.sy[y], sx = tb.sx[x];
   const int sy1 = min(sy + 1, h - 1), sx1 = min(sx + 1, w - 1);
-  const float r0 = __fadd_rn(__fmul_rn(m[sy * w + sx], tb.ax0[x]), __fmul_rn(m[sy * w + sx1], tb.ax1[x]));
-  const float r1 = __fadd_rn(__fmul_rn(m[sy1 * w + sx], tb.ax0[x]), __fmul_rn(m[sy1 * w + sx1], tb.ax1[x]));
-  return __fadd_rn(__fmul_rn(r0, tb.ay0[y]), __fmul_rn(r1, tb.ay1[y]));
+  const float r0 = add_rn(mul_rn(m[sy * w + sx], tb.ax0[x]), mul_rn(m[sy * w + sx1], tb.ax1[x]));
+  const float r1 = add_rn(mul_rn(m[sy1 * w + sx], tb.ax0[x]), mul_rn(m[sy1 * w + sx1], tb.ax1[x]));
+  return add_rn(mul_rn(r0, tb.ay0[y]), mul_rn(r1, tb.ay1[y]));
 }
 
 // pred value of pixel (y, x) given the map's min/max (normalize_img of -heatmap, then 1 - .)
 __device__ __forceinline__ float pred_at(const float* m, int h, int w, const EvalTabs& tb, int y, int x, float vmin,
                                          float vmax) {
   const float nh = -resized(m, h, w, tb, y, x);
-  const float rng = __fsub_rn(vmax, vmin);
-  const float v = rng != 0.f ? __fdiv_rn(__fsub_rn(nh, vmin), rng) : nh;
-  return __fsub_rn(1.f, v);
+  const float rng = sub_rn(vmax, vmin);
+  const float v = rng != 0.f ? div_rn(sub_rn(nh, vmin), rng) : nh;
+  return sub_rn(1.f, v);
 }
 
 __global__ __launch_bounds__(EV_T) void localize_ciou_kernel(const float* __restrict__ A, int h, int w, int S,
@@ -172,6 +173,73 @@ __global__ __launch_bounds__(EV_T) void localize_ciou_kernel(const float* __rest
   }
 }
 
+// normalize_img(heatmap) value of a resized pixel r given the resized map's own min/max (utils.py:234-239)
+__device__ __forceinline__ float norm_at(float r, float vmin, float vmax) {
+  const float rng = sub_rn(vmax, vmin);
+  return rng != 0.f ? div_rn(sub_rn(r, vmin), rng) : r;
+}
+
+// The continuous map localize_ciou_kernel binarises, written out: out = resize (mode 0), normalize_img(resize)
+// (mode 1) or 1 - normalize_img(-resize) (mode -1: pred_at, the value the median thresholds).  One block per map;
+// the source map is staged in LDS when it fits (HM_LDS floats; the network's maps are 14 x 14), else read in place.
+constexpr int HM_LDS = 4096;
+
+__global__ __launch_bounds__(EV_T) void heatmap_upsample_kernel(const float* __restrict__ A, int h, int w, int S,
+                                                                int mode, float* __restrict__ out) {
+  __shared__ EvalTabs tb;
+  __shared__ float src[HM_LDS];
+  __shared__ float fred[2][EV_T / 64];
+  const int img = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const float* m = A + (size_t)img * h * w;
+  const int n = S * S;
+  if (h * w <= HM_LDS) {
+    for (int i = tid; i < h * w; i += EV_T) src[i] = m[i];
+    m = src;
+  }
+  for (int d = tid; d < S; d += EV_T) {
+    lin_coef(d, h, S, tb.sy[d], tb.ay0[d], tb.ay1[d]);
+    lin_coef(d, w, S, tb.sx[d], tb.ax0[d], tb.ax1[d]);
+  }
+  __syncthreads();
+  float vmin = 0.f, vmax = 0.f;
+  if (mode != 0) {
+    // min / max of the resized map (mode 1) or of its negative (mode -1, as localize_ciou_kernel takes them)
+    float mn = INFINITY, mx = -INFINITY;
+    for (int i = tid; i < n; i += EV_T) {
+      const float r = resized(m, h, w, tb, i / S, i % S);
+      const float v = mode < 0 ? -r : r;
+      mn = fminf(mn, v);
+      mx = fmaxf(mx, v);
+    }
+    for (int o = 32; o >= 1; o >>= 1) {
+      mn = fminf(mn, __shfl_xor(mn, o, 64));
+      mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+    }
+    if (lane == 0) {
+      fred[0][wv] = mn;
+      fred[1][wv] = mx;
+    }
+    __syncthreads();
+    vmin = fred[0][0], vmax = fred[1][0];
+    for (int k = 1; k < EV_T / 64; ++k) {
+      vmin = fminf(vmin, fred[0][k]);
+      vmax = fmaxf(vmax, fred[1][k]);
+    }
+  }
+  float* o = out + (size_t)img * n;
+  for (int i = tid; i < n; i += EV_T) {
+    const int y = i / S, x = i % S;
+    float v;
+    if (mode == 0)
+      v = resized(m, h, w, tb, y, x);
+    else if (mode > 0)
+      v = norm_at(resized(m, h, w, tb, y, x), vmin, vmax);
+    else
+      v = pred_at(m, h, w, tb, y, x, vmin, vmax);
+    o[i] = v;
+  }
+}
+
 // cal_CIOU(p[i], p[i+1], 0.5) of binary maps (utils.mTC): one block per pair
 __global__ __launch_bounds__(EV_T) void pair_ciou_kernel(const unsigned char* __restrict__ p, int n,
                                                          double* __restrict__ out) {
@@ -223,6 +291,20 @@ extern "C" int avt_localize_ciou(const float* A, int N, int h, int w, int S, con
   hipLaunchKernelGGL(localize_ciou_kernel, dim3(N), dim3(EV_T), 0, (hipStream_t)stream, A, h, w, S, gt, out,
                      (unsigned char*)pred_out);
   return check_launch("localize_ciou");
+}
+
+// A [N][h][w] fp32 heatmaps -> out [N][S][S] fp32: the cv2 INTER_LINEAR resize of avt_localize_ciou, plain
+// (normalize 0), normalize_img'd over each map's own min/max (1), or as the pred the test loops threshold,
+// 1 - normalize_img(-resize) (-1).  A constant map is left unnormalised, as normalize_img's `if` leaves it.
+extern "C" int avt_heatmap_upsample(const float* A, int N, int h, int w, int S, int normalize, float* out,
+                                    void* stream) {
+  AVT_REQUIRE(A && out, "heatmap_upsample: null pointer");
+  AVT_REQUIRE(N >= 1 && h >= 1 && w >= 1 && S >= 2 && S <= EV_SMAX && (long long)h * w <= 0x7fffffffLL,
+              "heatmap_upsample: bad shape N=%d h=%d w=%d S=%d", N, h, w, S);
+  AVT_REQUIRE(normalize >= -1 && normalize <= 1, "heatmap_upsample: normalize must be 0, 1 or -1, got %d", normalize);
+  hipLaunchKernelGGL(heatmap_upsample_kernel, dim3(N), dim3(EV_T), 0, (hipStream_t)stream, A, h, w, S, normalize,
+                     out);
+  return check_launch("heatmap_upsample");
 }
 
 // out[k] = cal_CIOU(p[k], p[k+1], 0.5) for k < N-1 over binary maps p [N][n] u8 (utils.mTC).

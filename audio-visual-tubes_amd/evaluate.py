@@ -50,6 +50,31 @@ def localize(A: torch.Tensor, gt: Optional[torch.Tensor] = None, size: int = GT_
     return stats, maps
 
 
+_HEATMAP_MODES = {"resize": 0, "norm": 1, "pred": -1}
+
+
+def heatmaps(A: torch.Tensor, size: int = GT_SIZE, mode: str = "norm") -> torch.Tensor:
+    """The continuous map ``localize`` binarises, [N,size,size] fp32 on the device, from A [N,1,h,w] or [N,h,w]:
+    ``cv2.resize(A[i,0], (size, size), INTER_LINEAR)`` as it is (mode "resize"), ``normalize_img`` of it over its
+    own min and max (mode "norm": what test.py:102-111 draws), or ``1 - normalize_img(-resize)`` (mode "pred": the
+    value the test loops threshold at its median).  Same arithmetic, bit for bit, as inside ``localize``."""
+    if mode not in _HEATMAP_MODES:
+        raise ValueError(f"avt: heatmaps mode must be one of {sorted(_HEATMAP_MODES)}, got {mode!r}")
+    if not A.is_cuda:
+        raise RuntimeError("avt: heatmaps runs on the GPU (no CPU path)")
+    if A.dim() == 4:
+        if A.shape[1] != 1:
+            raise ValueError(f"avt: heatmaps must be [N,1,h,w], got {tuple(A.shape)}")
+        A = A[:, 0]
+    if A.dim() != 3:
+        raise ValueError(f"avt: heatmaps must be [N,h,w], got {tuple(A.shape)}")
+    N, h, w = A.shape
+    A = A.detach().contiguous().float()
+    out = torch.empty(N, size, size, device=A.device, dtype=torch.float32)
+    call("avt_heatmap_upsample", P(A), N, h, w, size, _HEATMAP_MODES[mode], P(out), stream_ptr())
+    return out
+
+
 def mtc(pred_maps: torch.Tensor) -> float:
     """utils.mTC (utils.py:311-318): mean cIoU(pred_i, pred_{i+1}, 0.5) over consecutive frames,
     from ``localize(..., return_maps=True)`` maps [T,S,S] of one clip."""
@@ -140,3 +165,61 @@ def evaluate_hardway(model, batches, gt_maps) -> Tuple[float, float]:
     finally:
         model.train(was_training)
     return ev.final(), ev.cal_AUC()
+
+
+def tube_indices(T: int, sampling_rate: int) -> list:
+    """The frames the per-video protocol samples (train_3D.py:152): every sampling_rate-th, the first and last left out."""
+    return list(range(sampling_rate, T - 1, sampling_rate))
+
+
+@torch.no_grad()
+def evaluate_tube(model, videos, sampling_rate: int = 16, render_to=None) -> dict:
+    """The per-video test loop of tube training (train_3D.py:146-186; flow.py:170-210 for AVENet).  ``videos`` yields
+    (frames [1,3,T,H,W], spec [1,1,F,Tt], gt [n,224,224]) with one gt map per sampled frame, or (name, frames, spec,
+    gt).  Per video: one eval-mode forward of ``frames[:, :, tube_indices(T, sampling_rate)]`` with the one
+    spectrogram (``FullModel``, folded if enabled; an ``AVENet`` runs frame by frame, each with that spectrogram),
+    ``localize`` of the n heat maps against gt, cIoU@0.5 and the 21-point AUC over those n frames, and mTC over the
+    consecutive predictions.  Returns ``dict(ciou=, auc=, mtc=, per_video=[dict(name=, ciou=, auc=, mtc=, cious=)])``,
+    the three headline numbers the means over the videos.  A video with fewer than two sampled frames has no mTC:
+    ValueError.  ``render_to(name, images)``, when given, receives ``render.overlay(sampled frames, pred=maps, gt=gt)``
+    ([n,H,W,3] uint8 on the device) per video; it needs frames of the gt maps' size.
+
+    The reference's tube loop resizes ``heatmap[step][0, 0]`` -- one row of the step-th map (train_3D.py:157-158).
+    This is the per-frame protocol every other loop of the reference runs: the whole map of each sampled frame."""
+    from .model import AVENet
+
+    per_frame = isinstance(model, AVENet)
+    was_training = model.training
+    model.eval()
+    per_video = []
+    try:
+        for k, item in enumerate(videos):
+            name, frames, spec, gt = item if len(item) == 4 else (k, *item)
+            if frames.dim() != 5 or frames.shape[0] != 1:
+                raise ValueError(f"avt: evaluate_tube takes one video at a time, frames [1,3,T,H,W], got "
+                                 f"{tuple(frames.shape)}")
+            idx = tube_indices(frames.shape[2], sampling_rate)
+            if len(idx) < 2:
+                raise ValueError(f"avt: video {name!r}: {frames.shape[2]} frames at sampling_rate {sampling_rate} give "
+                                 f"{len(idx)} sampled frame(s); mTC needs at least two frames")
+            sampled = frames[:, :, idx].float()
+            spec = spec.float()
+            if per_frame:
+                A = torch.cat([model(sampled[:, :, j].contiguous(), spec)[0] for j in range(len(idx))])
+            else:
+                A = model(spec, sampled)[0]
+            stats, maps = localize(A, torch.as_tensor(gt), return_maps=True)
+            cious = stats[:, 0].tolist()
+            per_video.append(dict(name=name, ciou=float(np.mean(np.array(cious) >= 0.5)), auc=auc_from_cious(cious),
+                                  mtc=mtc(maps), cious=cious))
+            if render_to is not None:
+                from . import render
+
+                render_to(name, render.overlay(sampled, pred=maps, gt=gt))
+    finally:
+        model.train(was_training)
+    if not per_video:
+        raise ValueError("avt: evaluate_tube got no video")
+    out = {k: float(np.sum([v[k] for v in per_video]) / len(per_video)) for k in ("ciou", "auc", "mtc")}
+    out["per_video"] = per_video
+    return out

@@ -45,6 +45,9 @@
  *   avt_ncthw_to_nhwc_bf16       einops 'b c t h w -> (b t) c h w' of the frames (train_hardway.py:130-131)
  *   avt_localize_ciou,           the test loops' heatmap -> cIoU protocol (train_hardway_1frame.py:195-206,
  *   avt_pair_ciou                utils.Evaluator.cal_CIOU utils.py:209-214, utils.mTC 311-318)
+ *   avt_heatmap_upsample         the continuous map of that protocol: cv2.resize + normalize_img (test.py:102-111)
+ *   avt_render_overlay           save_image / save_labels: frame + colour-mapped maps -> uint8 HWC (train_3D.py:73-81,
+ *                                flow.py:71-84)
  *   avt_spectrogram              the dataset's scipy.signal.spectrogram + log + Normalize(0, 12)
  *   avt_frames_transform         the dataset's frame transform: PIL BICUBIC Resize + crop + flip + ToTensor +
  *                                Normalize (datasets/dataloader.py:47-62)
@@ -459,6 +462,26 @@ int avt_localize_ciou(const float* A, int N, int h, int w, int S, const float* g
                       void* stream);
 /* out[k] = cIoU(p[k], p[k+1], 0.5) of binary maps p [N][n] u8, k < N-1 (utils.mTC) */
 int avt_pair_ciou(const void* p, int N, int n, double* out, void* stream);
+/* The continuous map avt_localize_ciou binarises, written out: A [N][h][w] -> out [N][S][S] fp32 by the same cv2
+ * INTER_LINEAR arithmetic (half-pixel centres, edges clamped with zero weight, horizontal then vertical pass,
+ * separately rounded fp32 products and sums).  normalize 0: the plain resize; 1: normalize_img(resize) over each
+ * map's own min and max (utils.py:234-239; a constant map is left as it is); -1: 1 - normalize_img(-resize), the
+ * `pred` the test loops threshold at its median (test.py:102-111 shows it).  2 <= S <= 512. */
+int avt_heatmap_upsample(const float* A, int N, int h, int w, int S, int normalize, float* out, void* stream);
+
+/* ---- qualitative output (save_image: visualize.py:46-50, train_3D.py:73-81; save_labels: flow.py:80-84) ---- */
+/* img [N][3][H][W] fp32 (the network's normalised frames) -> out [N][H][W][3] u8.  Per frame, vmin / vmax over its
+ * 3 H W values; n = (x - vmin) / (vmax - vmin) (n = x when they are equal), a = fp32(fp32(n * 255) * wimg).  Per
+ * layer k, c_k = lut[u8(map_k * scale_k)][ch] (fp32 product, truncated, clamped to [0, 255]); map_k [N][H][W] fp32
+ * or NULL, lut [256][3] u8.  out = u8(trunc(double(a) + (c0 * 0.5 + c1 * 0.5) * w0)) with both layers (save_image;
+ * w1 is not used and must be 0), u8(trunc(double(a) + c0 * w0)) with map0 alone (save_labels), u8(trunc(a)) with
+ * none: the bytes numpy 2.x gives for the reference's expression.  Sums outside [0, 255] saturate (numpy's cast of
+ * them is undefined).  Channel ch of the table goes to channel ch of the frame: with cv2's BGR table on an RGB
+ * frame, as in the reference, the jet colours come out mirrored (hot = blue).  map1 without map0, a layer without
+ * lut and non-positive sizes are refused. */
+int avt_render_overlay(const float* img, int N, int H, int W, const float* map0, float scale0, double w0,
+                       const float* map1, float scale1, double w1, float wimg, const unsigned char* lut,
+                       unsigned char* out, void* stream);
 
 /* ---- audio front end (datasets/dataloader.py:86-96): waveform -> normalised log-spectrogram ---- */
 /* segments of a length-N waveform at hop = nperseg - noverlap (the reference: 512 - 1) */
