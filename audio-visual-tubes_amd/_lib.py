@@ -109,6 +109,7 @@ SIGNATURES = {
     "avt_conv3d_fwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "avt_conv3d_fwd_bias": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _I, _P]),
     "avt_conv_fwd_plan": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "avt_conv_wgrad_plan": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "avt_fold3d_desc_bytes": (_Z, []),
     "avt_fold_conv3d_bn_batched": (_I, [_P, _I, _I, _I, _P]),
     "avt_video_stem_im2col": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),

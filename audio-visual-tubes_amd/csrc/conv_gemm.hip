@@ -456,17 +456,10 @@ static int stem_enabled() {
 }
 
 static int g_stem_wgrad = -1;  // 7x7/s2 stem wgrads on conv_stem_wgrad_kernel: -1 = env AVT_STEM_WGRAD (default 1)
-static int stem_wgrad_enabled() {
-  if (g_stem_wgrad < 0) {
-    const char* e = getenv("AVT_STEM_WGRAD");
-    g_stem_wgrad = e ? atoi(e) : 1;
-  }
-  return g_stem_wgrad;
-}
 
 static int g_nt64_config = -1;  // tile config of the pipelined NT kernel for 64-wide GEMM N (A/B knob; -1 auto)
 static int g_nt128_config = -1; // ... and for GEMM N % 128 == 0 (-1: by GEMM M, see plan_nt)
-static int g_wgrad_blocks = 0;     // wgrad split-K: 0 = wave model (wgrad_plan), >0 = fixed block target
+static int g_wgrad_blocks = 0;     // wgrad split-K: 0 = wave model (plan_wgrad_gemm), >0 = fixed block target
 static int g_wgrad_min_kt = 4;
 // largest split count that goes through a slab (deterministic: split partials summed in split order); beyond it
 // fp32 atomics (non-deterministic summation order; an A/B knob only: AVT_WGRAD_SLAB_MAX / avt_set_wgrad_slab_max)
@@ -1695,120 +1688,6 @@ extern "C" int avt_conv3d_dgrad(const void* dy, const void* wt, void* dx, const 
   return check_launch("conv3d_dgrad");
 }
 
-// wgrad launch plan: tile shape, split-K and (pipelined kernel) the fp32 partial slab it needs.
-struct WgradPlan {
-  GemmTNParams p;
-  int BM, BN, tiles, splits;
-  int nst;              // LDS ring stages of the pipelined kernel
-  int kg;               // wave groups per block splitting its k range (conv_tn_pipe_kernel KG)
-  bool pipe;            // LDS-DMA pipelined kernel (C % 8 == 0) vs register-staged (stems)
-  size_t slab_bytes;    // splits * Mg * Ng * 4 when split-K partials go through a slab
-};
-
-static WgradPlan wgrad_plan(int N, int H, int W, int Cp, int Creal, int K, int R, int S, int stride, int pad) {
-  static bool env_read = false;  // A/B knobs: AVT_WGRAD_SLAB_MAX, AVT_WGRAD_WAVE_COST (as avt_set_wgrad_slab_max)
-  if (!env_read) {
-    env_read = true;
-    if (const char* e = getenv("AVT_WGRAD_SLAB_MAX")) g_wgrad_slab_max = atoi(e);
-    if (const char* e = getenv("AVT_WGRAD_WAVE_COST")) g_wgrad_wave_cost = atoi(e);
-  }
-  WgradPlan pl{};
-  GemmTNParams& p = pl.p;
-  p.Mg = K;
-  p.H = H; p.W = W; p.Cp = Cp; p.Creal = Creal;
-  p.P = conv_out(H, R, stride, pad);
-  p.Q = conv_out(W, S, stride, pad);
-  p.R = R; p.S = S; p.stride = stride; p.pad = pad;
-  p.Kred = N * p.P * p.Q;
-  const int ncols = R * S * Cp;
-  pl.pipe = (Cp % 8 == 0) && conv_variant() == 1;
-  pl.BN = (ncols % 128 == 0 || ncols > 128) ? 128 : 64;
-  pl.BM = (K % 128 == 0 && Cp % 8 == 0) || (K % 128 == 0 && Cp == 4) ? 128 : 64;
-  // 8-wave 256-wide tiles halve the LDS fill bytes per flop where the GEMM is wide enough
-  // (layer4: K_out 512, R*S*C >= 2304); split-K supplies the parallelism
-  if (g_wgrad_big < 0) g_wgrad_big = getenv("AVT_WGRAD_BIG") ? atoi(getenv("AVT_WGRAD_BIG")) : 1;
-  if (pl.pipe && g_wgrad_big) {
-    if (K % 256 == 0 && K >= 512 && pl.BN == 128) pl.BM = 256;  // measured: a loss on layer3 (K_out 256)
-    if (ncols >= 2048 && pl.BM == 256) pl.BN = 256;
-  }
-  p.Ng = ((ncols + pl.BN - 1) / pl.BN) * pl.BN;
-  pl.tiles = (p.Mg / pl.BM) * (p.Ng / pl.BN);
-  const int nkt = (p.Kred + 31) / 32;
-  // Split-K count.  The grid runs in "waves" of resident blocks (CUs x blocks per CU, set by the
-  // ring's LDS: 4 stages x 32 pixels x (BM+BN) bf16 for the 4-wave tiles, 3 stages for the 8-wave
-  // ones, whose 256x256 form is also held to one block per CU by its registers).  For w = 1..4
-  // waves take the largest split count that fits, s_w = floor(w*slots/tiles), and keep the one
-  // with the least w * (ceil(nkt/s_w) + wave_cost) -- k-tiles per block plus its fixed
-  // prologue/epilogue cost.
-  // 1x1 convs (the downsample shortcuts): a k-tile is only 32 pixels x (BM + BN) operand rows while
-  // the epilogue still writes a BM x BN fp32 tile, so blocks need deeper K ranges than the wave
-  // model picks (measured, tools/conv_bench.py: min 24 k-tiles takes the six downsample wgrads from
-  // 0.239 to 0.143 ms at B = 128; the 3x3 shapes keep their optimum at 4)
-  static const int min_kt_1x1 = getenv("AVT_WGRAD_MIN_KT_1X1") ? atoi(getenv("AVT_WGRAD_MIN_KT_1X1")) : 24;
-  const int min_kt = (R * S == 1) ? max(g_wgrad_min_kt, min_kt_1x1) : g_wgrad_min_kt;
-  int splits;
-  const bool big = pl.BM == 256 || pl.BN == 256;
-  // ring depth: 4 stages (4-wave tiles: two blocks per CU at 128 x 128) / 3 (8-wave); a deeper ring
-  // (AVT_WGRAD_NST / AVT_WGRAD_NST_BIG, or avt_set_wgrad_nst) keeps more k-tiles in flight for a
-  // block alone on its CU -- the small-batch regime, where a block's k range is short and its DMA
-  // latency is exposed (one stage = 32 pixels x (BM + BN) bf16)
-  if (g_wgrad_nst < 0) g_wgrad_nst = getenv("AVT_WGRAD_NST") ? atoi(getenv("AVT_WGRAD_NST")) : 4;
-  if (g_wgrad_nst_big < 0) g_wgrad_nst_big = getenv("AVT_WGRAD_NST_BIG") ? atoi(getenv("AVT_WGRAD_NST_BIG")) : 3;
-  // (the 256 x 128 8-wave tile always runs the 3-stage ring, launch_tn: nst_big is the 256 x 256 tile's)
-  pl.nst = (pl.BM == 256 && pl.BN == 256) ? g_wgrad_nst_big : big ? 3 : g_wgrad_nst;
-  if (g_wgrad_blocks > 0) {
-    splits = g_wgrad_blocks / pl.tiles;
-  } else {
-    int occ = max(1, 163840 / (pl.nst * 64 * (pl.BM + pl.BN)));
-    if (pl.BM == 256 && pl.BN == 256) occ = 1;
-    // The share of the chip's block slots the model assumes the wgrad has: with both trunks' backward on two streams a
-    // wgrad shares the chip with the other trunk's kernels, and fewer splits mean fewer partials through the slab and
-    // a shorter reduce.  Auto (default): 65 % for a batch of <= 32, 75 % for <= 64, else 100 % -- measured same-box
-    // (profiles/r6_ab_wgrad_slots*.txt): 65 % is +3.3 % at B=32, 75 % +0.7 % at B=64, and 50 % -1.8 % at B=128.
-    // AVT_WGRAD_SLOTS_PCT / avt_set_wgrad_slots_pct fix it (1-100; 0 = auto).
-    if (g_wgrad_slots_pct < 0) g_wgrad_slots_pct = getenv("AVT_WGRAD_SLOTS_PCT") ? atoi(getenv("AVT_WGRAD_SLOTS_PCT")) : 0;
-    const int slots_pct = g_wgrad_slots_pct > 0 ? min(g_wgrad_slots_pct, 100) : N <= 32 ? 65 : N <= 64 ? 75 : 100;
-    const long long slots = max(1LL, (long long)num_cus() * occ * slots_pct / 100);
-    long long best = -1;
-    splits = 1;
-    for (int w = 1; w <= 4; ++w) {
-      const int s_w = (int)(w * slots / pl.tiles);
-      if (s_w < 1) continue;
-      const int kps_w = max(min_kt, (nkt + s_w - 1) / s_w);
-      const long long waves = (((long long)pl.tiles * ((nkt + kps_w - 1) / kps_w)) + slots - 1) / slots;
-      const long long cost = waves * (kps_w + g_wgrad_wave_cost);
-      if (best < 0 || cost < best) {
-        best = cost;
-        splits = s_w;
-      }
-    }
-  }
-  if (splits < 1) splits = 1;
-  int kps = (nkt + splits - 1) / splits;
-  if (kps < min_kt) kps = min_kt;
-  pl.splits = (nkt + kps - 1) / kps;
-  // two wave groups per block (AVT_WGRAD_KG, default 2): the pairs of blocks the plan puts on one CU
-  // become one 8-wave block over both k ranges with ONE partial tile -- half the split-K slab bytes
-  // (or atomics) at the same waves per CU; 4-wave tiles on the 4-stage ring (2 x 64 KB of LDS at 128 x 128)
-  static const int kg_env = getenv("AVT_WGRAD_KG") ? atoi(getenv("AVT_WGRAD_KG")) : 2;
-  pl.kg = 1;
-  const int pair_occ = 163840 / (pl.nst * 64 * (pl.BM + pl.BN));  // 4-wave blocks per CU (2 at 128 x 128)
-  // (3x3 only: the 1x1 shortcuts' deep k ranges lost 25-30 % at B = 128 as pairs)
-  if (kg_env >= 2 && pl.pipe && !big && pl.nst == 4 && pair_occ == 2 && pl.splits >= 2 && R * S > 1) {
-    pl.kg = 2;
-    kps *= 2;
-    pl.splits = (nkt + kps - 1) / kps;
-  }
-  p.kt_per_split = kps;
-  // slab + reduce pass for moderate split counts (measured faster on layer3/4); very deep splits
-  // (layer1/2: 100-200 splits of a small output) keep the fp32 atomics, which overlap the compute
-  // (the slab holds whole tiles in register order: splits x Mg x Ng, conv_tn_pipe.h)
-  pl.slab_bytes = (pl.pipe && pl.splits > 1 && pl.splits <= g_wgrad_slab_max)
-                      ? (size_t)pl.splits * p.Mg * p.Ng * sizeof(float)
-                      : 0;
-  return pl;
-}
-
 // Deferred split-K reduces, batched (avt_wgrad_reduce_batch): a trunk's wgrads leave their slabs (avt_conv2d_wgrad_defer)
 // and one launch sums all of them at the end of the trunk's backward segment -- blockIdx.y = the slab, a grid-stride
 // loop over its float4 positions; per position the splits in order, 8 loads in flight: the order of
@@ -1915,117 +1794,108 @@ static const void* pixtab_lookup(int N, int H, int W, int Cp, int R, int S, int 
   return nullptr;
 }
 
-template <int WM, int WN, int TM, int TN, int NST, int KG>
-static void launch_tn_one(dim3 grid, const GemmTNPipeParams& pp, hipStream_t st) {
-  const dim3 block(WM * WN * 64 * KG);
-  if (pp.tab != nullptr) {
-    if (pp.cnt != nullptr)
-      hipLaunchKernelGGL((conv_tn_pipe_kernel<WM, WN, TM, TN, NST, KG, true, true>), grid, block, 0, st, pp);
-    else
-      hipLaunchKernelGGL((conv_tn_pipe_kernel<WM, WN, TM, TN, NST, KG, false, true>), grid, block, 0, st, pp);
-  } else if (pp.cnt != nullptr) {
-    hipLaunchKernelGGL((conv_tn_pipe_kernel<WM, WN, TM, TN, NST, KG, true>), grid, block, 0, st, pp);
-  } else {
-    hipLaunchKernelGGL((conv_tn_pipe_kernel<WM, WN, TM, TN, NST, KG>), grid, block, 0, st, pp);
-  }
-}
-
-// the wgrad plan's launch shape runs the fused in-kernel slab reduce (launch_tn_one; the deeper-ring A/B variants
-// keep the separate reduce)
-static bool tn_fusable(const WgradPlan& pl) {
-  if (!pl.pipe || pl.splits < 2) return false;
-  if (pl.BM == 256 && pl.BN == 256) return pl.nst < 4;
-  if (pl.BM == 256) return true;
-  return pl.kg == 2 || pl.nst < 6;
-}
-
-template <int CVEC, int BM, int BN>
-static void launch_tn(const WgradPlan& pl, float* slab, hipStream_t st, int* tickets = nullptr) {
-  GemmTNParams p = pl.p;
-  if (pl.pipe) {
-    GemmTNPipeParams pp;
-    pp.p = p;
-    pp.div_pq = make_magic((unsigned)(p.P * p.Q));
-    pp.div_q = make_magic((unsigned)p.Q);
-    pp.dy_bytes = (unsigned)((size_t)p.Kred * p.Mg * 2);
-    pp.x_bytes = (unsigned)((size_t)(p.Kred / (p.P * p.Q)) * p.H * p.W * p.Cp * 2);
-    pp.slab = slab;
-    pp.cnt = (slab != nullptr && tickets != nullptr && tn_fusable(pl)) ? tickets : nullptr;
-    pp.slab_bytes = (unsigned)pl.slab_bytes;
-    pp.splits = pl.splits;
-    // the registered per-pixel table of this geometry (launch_tn_one's instantiations read it; the deeper-ring A/B
-    // variants below keep the in-loop arithmetic)
-    pp.tab = pixtab_geometry_ok(p.Kred / (p.P * p.Q), p.H, p.W, p.R, p.S, p.stride, p.pad)
-                 ? pixtab_lookup(p.Kred / (p.P * p.Q), p.H, p.W, p.Cp, p.R, p.S, p.stride, p.pad)
-                 : nullptr;
-    const dim3 grid(pl.tiles * pl.splits);
-    if constexpr (BM == 256 && BN == 256) {
-      if (pl.nst >= 5)
-        hipLaunchKernelGGL((conv_tn_pipe_kernel<4, 2, 2, 4, 5>), grid, dim3(512), 0, st, pp);
-      else if (pl.nst == 4)
-        hipLaunchKernelGGL((conv_tn_pipe_kernel<4, 2, 2, 4, 4>), grid, dim3(512), 0, st, pp);
-      else
-        launch_tn_one<4, 2, 2, 4, 3, 1>(grid, pp, st);
-    } else if constexpr (BM == 256) {
-      launch_tn_one<4, 2, 2, 2, 3, 1>(grid, pp, st);
-    } else {
-      if (pl.kg == 2)
-        launch_tn_one<2, 2, BM / 64, BN / 64, 4, 2>(grid, pp, st);
-      else if (pl.nst >= 8)
-        hipLaunchKernelGGL((conv_tn_pipe_kernel<2, 2, BM / 64, BN / 64, 8>), grid, dim3(256), 0, st, pp);
-      else if (pl.nst >= 6)
-        hipLaunchKernelGGL((conv_tn_pipe_kernel<2, 2, BM / 64, BN / 64, 6>), grid, dim3(256), 0, st, pp);
-      else
-        launch_tn_one<2, 2, BM / 64, BN / 64, 4, 1>(grid, pp, st);
-    }
-    return;
-  }
-  if constexpr (BM <= 128)
-    hipLaunchKernelGGL((gemm_tn_kernel<CVEC, BM, BN>), dim3(pl.tiles, pl.splits), dim3(256), 0, st, p);
-}
-
-// ---- halo wgrad plan (conv_wgrad_halo.h) ----
+// ---- the 2-D weight gradient: plan_wgrad decides everything from the shape, the knobs and what the caller brought;
+// launch_wgrad names every instantiation once; avt_conv_wgrad_plan reports the plan without a GPU ----
 static int g_wgrad_halo_rw = -1;  // rows per wave of the K = 64 halo wgrad: 32 (default) or 64; -1: env AVT_WGRAD_HALO_RW
-static int wgrad_halo_rw() {
-  if (g_wgrad_halo_rw < 0) g_wgrad_halo_rw = getenv("AVT_WGRAD_HALO_RW") ? atoi(getenv("AVT_WGRAD_HALO_RW")) : 32;
-  return g_wgrad_halo_rw;
-}
-static int g_row3_min_kt = -1;  // ROW3 split floor (k-tiles per split); -1: env AVT_ROW3_MIN_KT
-static int row3_min_kt() {
-  if (g_row3_min_kt < 0) g_row3_min_kt = getenv("AVT_ROW3_MIN_KT") ? atoi(getenv("AVT_ROW3_MIN_KT")) : 8;
-  if (g_row3_min_kt < 1) g_row3_min_kt = 1;
-  return g_row3_min_kt;
-}
-static int g_row3_kg = -1;  // ROW3 k groups per block (1 or 2); -1: env AVT_ROW3_KG
-static int row3_kg() {
-  if (g_row3_kg < 0) g_row3_kg = getenv("AVT_ROW3_KG") ? atoi(getenv("AVT_ROW3_KG")) : 2;
-  return (g_row3_kg == 2 || g_row3_kg == 4) ? g_row3_kg : 1;
-}
-static int g_row3_pf = -1;  // ROW3 (KG 2): next tile's first fragments read behind the MFMAs (default: +3-4 %);
-                            // -1: env AVT_ROW3_PF
-static int row3_pf() {
-  if (g_row3_pf < 0) g_row3_pf = getenv("AVT_ROW3_PF") ? atoi(getenv("AVT_ROW3_PF")) : 1;
-  return g_row3_pf;
-}
-static int wgrad_halo_enabled() {
-  if (g_wgrad_halo < 0) {
-    const char* e = getenv("AVT_WGRAD_HALO");
-    g_wgrad_halo = e ? atoi(e) : 3;
-  }
-  return g_wgrad_halo;
+static int g_row3_min_kt = -1;    // ROW3 split floor (k-tiles per split); -1: env AVT_ROW3_MIN_KT (default 8)
+static int g_row3_kg = -1;        // ROW3 k groups per block (1, 2 or 4); -1: env AVT_ROW3_KG (default 2)
+static int g_row3_pf = -1;  // ROW3 (KG 2): next tile's first fragments read behind the MFMAs (default: +3-4 %); -1: env AVT_ROW3_PF
+// A/B knob: the fused slab reduce (conv_tn_pipe.h FUSED) for the tap-gather wgrads, avt_set_wgrad_fused / env
+// AVT_WGRAD_FUSED (0 default = the separate reduce launch; 1 = fused up to g_wgrad_fused_max_bytes of other splits'
+// partials per tile).  Bitwise equal where the separate reduce runs one wave per position, but SLOWER: the wgrad
+// family 355 -> 214 TF/s, the step -7 % at B=32 and -1.7 % at B=128 (profiles/r6_ab_wgrad_fused.txt) -- the
+// write-through partials and the last block's serial read of the other splits cost more than the reduce launch
+static int g_wgrad_fused = -1;
+static long long g_wgrad_fused_max_bytes = -1;
+
+// Every knob the wgrad plan reads, resolved in this one place at the top of plan_wgrad: a setter's value, else the
+// environment's (read at first use, and again after a setter's -1), else the default.
+struct WgKnobs {
+  int variant;  // conv_variant(): 1 = the LDS-DMA kernels
+  int stem, halo, halo_rw, halo_share, row3_wm, row3_min_kt, row3_kg, row3_pf;
+  int blocks, min_kt, min_kt_1x1, slab_max, wave_cost, big, nst, nst_big, slots_pct, kg, fused;
+  long long fused_max_bytes;
+};
+static WgKnobs wgrad_knobs() {
+  const auto env = [](const char* name, long long dflt) { return getenv(name) ? atoll(getenv(name)) : dflt; };
+  const auto lazy = [&env](int& g, const char* name, int dflt) { return g < 0 ? (g = (int)env(name, dflt)) : g; };
+  // read once per process: AVT_WGRAD_SLAB_MAX / _WAVE_COST (as avt_set_wgrad_slab_max) and the knobs without a setter
+  struct Once { int min_kt_1x1, kg, halo_share, row3_wm; };
+  static const Once once = [&env] {
+    g_wgrad_slab_max = (int)env("AVT_WGRAD_SLAB_MAX", g_wgrad_slab_max);
+    g_wgrad_wave_cost = (int)env("AVT_WGRAD_WAVE_COST", g_wgrad_wave_cost);
+    return Once{(int)env("AVT_WGRAD_MIN_KT_1X1", 24), (int)env("AVT_WGRAD_KG", 2),
+                (int)env("AVT_WGRAD_HALO_SHARE", 100), (int)env("AVT_ROW3_WM", 0)};
+  }();
+  WgKnobs k;
+  k.variant = conv_variant();
+  k.stem = lazy(g_stem_wgrad, "AVT_STEM_WGRAD", 1);
+  k.halo = lazy(g_wgrad_halo, "AVT_WGRAD_HALO", 3);
+  k.halo_rw = lazy(g_wgrad_halo_rw, "AVT_WGRAD_HALO_RW", 32);
+  k.halo_share = once.halo_share; k.row3_wm = once.row3_wm;  // (row3_wm 1, A/B: 64-row ROW3 blocks at K >= 128)
+  if (lazy(g_row3_min_kt, "AVT_ROW3_MIN_KT", 8) < 1) g_row3_min_kt = 1;
+  k.row3_min_kt = g_row3_min_kt;
+  lazy(g_row3_kg, "AVT_ROW3_KG", 2);
+  k.row3_kg = (g_row3_kg == 2 || g_row3_kg == 4) ? g_row3_kg : 1;
+  k.row3_pf = lazy(g_row3_pf, "AVT_ROW3_PF", 1);
+  k.blocks = g_wgrad_blocks; k.min_kt = g_wgrad_min_kt; k.min_kt_1x1 = once.min_kt_1x1;
+  k.slab_max = g_wgrad_slab_max; k.wave_cost = g_wgrad_wave_cost; k.kg = once.kg;
+  k.big = lazy(g_wgrad_big, "AVT_WGRAD_BIG", 1);
+  k.nst = lazy(g_wgrad_nst, "AVT_WGRAD_NST", 4);
+  k.nst_big = lazy(g_wgrad_nst_big, "AVT_WGRAD_NST_BIG", 3);
+  k.slots_pct = lazy(g_wgrad_slots_pct, "AVT_WGRAD_SLOTS_PCT", 0);
+  k.fused = lazy(g_wgrad_fused, "AVT_WGRAD_FUSED", 0);
+  if (g_wgrad_fused_max_bytes < 0) g_wgrad_fused_max_bytes = 1024LL * env("AVT_WGRAD_FUSED_MAX_KB", 2048);
+  k.fused_max_bytes = g_wgrad_fused_max_bytes;
+  return k;
 }
 
-struct WgradHaloPlan {
-  bool ok;
-  bool row3; // one filter row (3 taps) per block: WM x 2 waves of 64 x 96, strip of PR - 2 PW patch rows
-  int kg;    // ROW3: k groups per block (KG groups of WM x 2 waves on interleaved k-tiles, one partial per block;
-             // WM 2: at most 2)
-  int WM;    // 2: BM 128 (4 waves), 1: BM 64 (2 waves)
-  int RW;    // output channels per wave: 64, or 32 (9-tap form, K = 64: 4 waves of 32 x 288, two per SIMD)
-  WgradHaloArgs a;
-  size_t slab_bytes;
-  int groups, per_group;  // reduce: split groups (pass 1), then one ordered pass over the group heads
+// avt_conv_wgrad_plan's family and partials values (include/avt_tuning.h)
+enum { WG_STEM = 0, WG_HALO9 = 1, WG_ROW3 = 2, WG_GATHER = 3, WG_REG = 4 };
+enum { WG_SLAB_REDUCE = 0, WG_SLAB_FUSED = 1, WG_SLAB_DEFER = 2, WG_ATOMICS = 3 };
+
+struct WgShape { int N, H, W, Cp, Creal, K, R, S, stride, pad; };
+struct WgWs { size_t bytes; int tickets; bool defer; };  // what the caller brought (0 bytes, 0 tickets: none)
+// Plain data, no caller pointer: the pointer members of the three geometry blocks stay null, launch_wgrad fills copies.
+struct WgPlan {
+  int family;          // WG_STEM .. WG_REG
+  int wm, wn, tm, tn;  // waves per block and 32 x 32 tiles per wave (halo: tn = tap subtiles per wave; stem: wm = waves)
+  int rw, prmax;       // halo forms: output channels per wave, LDS patch rows
+  int nst;             // LDS ring stages of the instantiation launched
+  int kg, pf;          // k groups per block; ROW3 (KG 2) prefetch form
+  int tab;             // tap gather: the instantiation has a pixel-table form and the geometry a table layout
+  int splits, kt_per_split, tiles;  // grid = tiles x splits (stem: splits = blocks, each a partial; tiles = wave tiles)
+  int partials;        // WG_SLAB_REDUCE .. WG_ATOMICS
+  size_t slab_bytes;   // of the workspace, 0 without a slab
+  int tickets;         // of the caller's, WG_SLAB_FUSED only
+  int G, red_grid, red_block;  // the separate reduce: waves per 64 slab positions (native), grid and block (halo: of
+  int groups, per_group;       // the last pass, over `groups` heads of per_group splits each)
+  GemmTNParams g; WgradHaloArgs ha; StemWgradArgs sa;  // the family's geometry block: gather / register-staged, halo, stem
 };
+
+// Arm 1, the 7x7/s2 stems on conv_stem_wgrad_kernel: one block per CU at most, every block's partial in its own slab
+// entry -- so only with the workspace.  False: not such a stem, or no room (arm 3 takes it, register-staged, atomics).
+static bool plan_wgrad_stem(WgPlan& pl, const WgShape& s, const WgKnobs& k, const WgWs& ws) {
+  if (!((s.Cp == 4 || s.Cp == 1) && k.stem && s.K == 64 && s.R == 7 && s.S == 7 && s.stride == 2 && s.pad == 3 &&
+        s.Creal >= 1 && s.Creal <= s.Cp && s.N >= 1))
+    return false;
+  const int OH = conv_out(s.H, 7, 2, 3), OW = conv_out(s.W, 7, 2, 3);
+  const size_t x_bytes = (size_t)s.N * s.H * s.W * s.Cp * 2, dy_bytes = (size_t)s.N * OH * OW * 64 * 2;
+  if (OH < 1 || OW < 1 || x_bytes >= (1ull << 31) || dy_bytes >= (1ull << 31)) return false;  // (32-bit offsets)
+  const int nw = s.Cp == 4 ? StemWgradCfg<4>::NW : StemWgradCfg<1>::NW;
+  const int tiles_per_row = (OW + 31) / 32, total_tiles = s.N * OH * tiles_per_row;
+  const int grid = min((total_tiles + nw - 1) / nw, num_cus());
+  const size_t slab_bytes = (size_t)grid * 64 * 49 * s.Creal * sizeof(float);
+  if (ws.bytes < slab_bytes) return false;
+  StemWgradArgs& a = pl.sa;
+  a.x_bytes = (unsigned)x_bytes; a.dy_bytes = (unsigned)dy_bytes;
+  a.N = s.N; a.IH = s.H; a.IW = s.W; a.OH = OH; a.OW = OW; a.Creal = s.Creal;
+  a.tiles_per_row = tiles_per_row; a.total_tiles = total_tiles;
+  pl.family = WG_STEM; pl.wm = nw; pl.wn = 1; pl.nst = 2; pl.kg = 1;
+  pl.splits = grid; pl.tiles = total_tiles; pl.partials = WG_SLAB_REDUCE; pl.slab_bytes = slab_bytes;
+  pl.red_grid = (64 * 49 * s.Creal + 63) / 64; pl.red_block = 1024;
+  return true;
+}
 
 static constexpr int kRow3PrMax = 40;  // strip rows staged by the ROW3 form
 // default form 3 takes ROW3 from this many output pixels up (B = 128: 401 k vision / 624 k audio); below
@@ -2033,31 +1903,33 @@ static constexpr int kRow3PrMax = 40;  // strip rows staged by the ROW3 form
 // 100 k / 156 k pixels, -1.5 % per step in a same-box A/B)
 static constexpr long long kRow3MinPixels = 200000;
 
-static WgradHaloPlan wgrad_halo_plan(int N, int H, int W, int Cp, int Creal, int K, int R, int S, int stride, int pad) {
-  WgradHaloPlan pl{};
-  pl.ok = false;
-  int mode = wgrad_halo_enabled();
+// Arm 2, the 3x3/s1 convs on conv_wgrad_halo_kernel (conv_wgrad_halo.h): all nine taps per block (WG_HALO9), or one
+// filter row (3 taps) per block (WG_ROW3: WM x 2 waves of 64 x 96 per k group, a strip of PR - 2 PW patch rows).
+// False: the knob or the shape keeps the conv on arm 3.
+static bool plan_wgrad_halo(WgPlan& pl, const WgShape& s, const WgKnobs& k, const WgWs& ws) {
+  const int N = s.N, H = s.H, W = s.W, Cp = s.Cp, K = s.K;
+  int mode = k.halo;
   if (mode == 3) mode = (K == 64 && (long long)N * H * W >= kRow3MinPixels) ? 2 : 0;
-  if (!mode || R != 3 || S != 3 || stride != 1 || pad != 1 || Cp != Creal || Cp % 64 != 0 ||
-      K % 64 != 0 || conv_variant() != 1)
-    return pl;
-  WgradHaloArgs& a = pl.a;
+  if (!mode || s.R != 3 || s.S != 3 || s.stride != 1 || s.pad != 1 || Cp != s.Creal || Cp % 64 != 0 || K % 64 != 0 ||
+      k.variant != 1)
+    return false;
+  WgradHaloArgs a{};
   a.N = N; a.H = H; a.W = W; a.C = Cp; a.K = K;
-  pl.row3 = mode == 2;
-  pl.kg = 1;
-  pl.WM = (K % 128 == 0) ? 2 : 1;
-  pl.RW = 64;
-  if (!pl.row3 && K == 64 && wgrad_halo_rw() == 32) {  // 4 waves of 32 x 288 (144 accumulator registers: two waves per SIMD)
-    pl.WM = 2;
-    pl.RW = 32;
+  const bool row3 = mode == 2;
+  int WM = (K % 128 == 0) ? 2 : 1;  // 2: BM 128 (4 waves), 1: BM 64 (2 waves)
+  int RW = 64;                      // output channels per wave
+  if (!row3 && K == 64 && k.halo_rw == 32) {  // 4 waves of 32 x 288 (144 accumulator registers: two waves per SIMD)
+    WM = 2;
+    RW = 32;
   }
-  if (pl.row3 && getenv("AVT_ROW3_WM") && atoi(getenv("AVT_ROW3_WM")) == 1) pl.WM = 1;  // A/B: 64-row blocks at K >= 128
-  const int BM = pl.WM * pl.RW;  // after every WM override: the plan and the launch use the same block rows
-  const int ncols = pl.row3 ? 192 : 576;  // GEMM columns per block
-  const int PRMAX = pl.row3 ? kRow3PrMax : (pl.WM == 2 && pl.RW == 64) ? 160 : 72;
-  if (pl.row3) pl.kg = pl.WM == 1 ? row3_kg() : (row3_kg() >= 2 ? 2 : 1);
-  const int per_cu = pl.row3 ? (pl.WM == 1 ? 4 : 2) / pl.kg : (pl.WM == 2 && pl.RW == 64) ? 1 : 2;  // resident blocks per CU
-  auto staged = [&](int pr, int pw) { return pl.row3 ? pr - 2 * pw : pr; };
+  if (row3 && k.row3_wm == 1) WM = 1;
+  const int BM = WM * RW;  // after every WM override: the plan and the launch use the same block rows
+  const int ncols = row3 ? 192 : 576;  // GEMM columns per block
+  const int PRMAX = row3 ? kRow3PrMax : (WM == 2 && RW == 64) ? 160 : 72;
+  // ROW3: KG groups of WM x 2 waves on interleaved k-tiles, one partial per block (WM 2: at most 2)
+  const int kg = !row3 ? 1 : WM == 1 ? k.row3_kg : (k.row3_kg >= 2 ? 2 : 1);
+  const int per_cu = row3 ? (WM == 1 ? 4 : 2) / kg : (WM == 2 && RW == 64) ? 1 : 2;  // resident blocks per CU
+  auto staged = [&](int pr, int pw) { return row3 ? pr - 2 * pw : pr; };
   const double t_mfma = 2.0 * 32 * BM * ncols / (4 * 1024.0);
   auto cost = [&](long long tiles, int pr) {  // pr: staged patch rows
     const double fill = (32.0 * BM * 2 + pr * 128.0) / (29.0 / per_cu);
@@ -2068,7 +1940,7 @@ static WgradHaloPlan wgrad_halo_plan(int N, int H, int W, int Cp, int Creal, int
   {
     const int span = (W >= 32 ? 2 : (31 + W - 1) / W + 1);
     const int pr = (span + 2) * (W + 2);
-    if (!pl.row3 && staged(pr, W + 2) <= PRMAX) {  // (ROW3: windows only -- fixed fragment rows)
+    if (!row3 && staged(pr, W + 2) <= PRMAX) {  // (ROW3: windows only -- fixed fragment rows)
       const long long tiles = (long long)(H * W + 31) / 32;
       best = cost(tiles, staged(pr, W + 2));
       a.raster = 1; a.R = 1; a.CW = 32; a.lcw = 5; a.wcols = 1; a.tiles_img = (int)tiles; a.PW = W + 2; a.PR = pr;
@@ -2087,15 +1959,14 @@ static WgradHaloPlan wgrad_halo_plan(int N, int H, int W, int Cp, int Creal, int
       a.PW = cw + 2; a.PR = pr;
     }
   }
-  if (best < 0) return pl;
+  if (best < 0) return false;
   a.nkt = N * a.tiles_img;
-  const int per_split = (K / BM) * (Cp / 64) * (pl.row3 ? 3 : 1);
+  const int per_split = (K / BM) * (Cp / 64) * (row3 ? 3 : 1);
   // (A/B, env AVT_WGRAD_HALO_SHARE, default 100: the share of the chip's block slots the split count assumes)
-  static const int halo_share = getenv("AVT_WGRAD_HALO_SHARE") ? atoi(getenv("AVT_WGRAD_HALO_SHARE")) : 100;
-  const long long slots = max(1LL, (long long)num_cus() * per_cu * min(max(halo_share, 1), 100) / 100);
+  const long long slots = max(1LL, (long long)num_cus() * per_cu * min(max(k.halo_share, 1), 100) / 100);
   int splits = (int)(slots / per_split);
-  if (pl.row3) {  // at least row3_min_kt() k-tiles per split: the slab (splits x 147 KB at K 64) is the cost at small N
-    const int cap = a.nkt / row3_min_kt();
+  if (row3) {  // at least row3_min_kt k-tiles per split: the slab (splits x 147 KB at K 64) is the cost at small N
+    const int cap = a.nkt / k.row3_min_kt;
     if (splits > cap) splits = cap;
   }
   if (splits < 1) splits = 1;
@@ -2108,50 +1979,281 @@ static WgradHaloPlan wgrad_halo_plan(int N, int H, int W, int Cp, int Creal, int
   a.div_wcols = make_magic((unsigned)a.wcols);
   a.dy_bytes = (unsigned)((size_t)N * H * W * K * 2);
   a.x_bytes = (unsigned)((size_t)N * H * W * Cp * 2);
-  pl.slab_bytes = a.splits > 1 ? (size_t)a.splits * K * 9 * Cp * sizeof(float) : 0;
-  pl.per_group = 16;
-  pl.groups = (a.splits + pl.per_group - 1) / pl.per_group;
-  pl.ok = true;
+  pl.ha = a;
+  pl.family = row3 ? WG_ROW3 : WG_HALO9;
+  pl.wm = WM; pl.wn = 2; pl.tm = RW / 32; pl.tn = row3 ? 3 : 9;
+  pl.rw = RW; pl.prmax = PRMAX; pl.nst = row3 ? 4 : (WM == 2 && RW == 64) ? 5 : 6;
+  pl.kg = kg; pl.pf = row3 && WM == 1 && kg == 2 && k.row3_pf;
+  pl.splits = a.splits; pl.kt_per_split = kps; pl.tiles = per_split;
+  // without the workspace the split partials are added with fp32 atomics
+  const size_t want = a.splits > 1 ? (size_t)a.splits * K * 9 * Cp * sizeof(float) : 0;
+  pl.slab_bytes = ws.bytes >= want ? want : 0;
+  pl.partials = pl.slab_bytes > 0 ? WG_SLAB_REDUCE : WG_ATOMICS;
+  if (pl.slab_bytes > 0) {  // ordered: groups of per_group splits, then the group heads
+    pl.per_group = 16; pl.groups = (a.splits + pl.per_group - 1) / pl.per_group;
+    // the final pass is latency-bound (one thread per 4 outputs, a serial chain of entries): 64-thread blocks
+    pl.red_grid = (int)(((long long)K * 9 * Cp / 4 + 63) / 64); pl.red_block = 64;
+  }
+  return true;
+}
+
+// Arm 3, every other conv: the tap-gather kernel (conv_tn_pipe_kernel, C % 8 == 0), or the register-staged
+// gemm_tn_kernel (the stems without their workspace, and everything under avt_set_conv_variant(0)).
+static void plan_wgrad_gemm(WgPlan& pl, const WgShape& s, const WgKnobs& k, const WgWs& ws) {
+  const int N = s.N, Cp = s.Cp, K = s.K, R = s.R, S = s.S;
+  GemmTNParams& p = pl.g;
+  p.Mg = K; p.H = s.H; p.W = s.W; p.Cp = Cp; p.Creal = s.Creal;
+  p.P = conv_out(s.H, R, s.stride, s.pad);
+  p.Q = conv_out(s.W, S, s.stride, s.pad);
+  p.R = R; p.S = S; p.stride = s.stride; p.pad = s.pad;
+  p.Kred = N * p.P * p.Q;
+  const int ncols = R * S * Cp;
+  const bool pipe = (Cp % 8 == 0) && k.variant == 1;
+  int BN = (ncols % 128 == 0 || ncols > 128) ? 128 : 64;
+  int BM = (K % 128 == 0 && Cp % 8 == 0) || (K % 128 == 0 && Cp == 4) ? 128 : 64;
+  // 8-wave 256-wide tiles halve the LDS fill bytes per flop where the GEMM is wide enough
+  // (layer4: K_out 512, R*S*C >= 2304); split-K supplies the parallelism
+  if (pipe && k.big) {
+    if (K % 256 == 0 && K >= 512 && BN == 128) BM = 256;  // measured: a loss on layer3 (K_out 256)
+    if (ncols >= 2048 && BM == 256) BN = 256;
+  }
+  p.Ng = ((ncols + BN - 1) / BN) * BN;
+  pl.tiles = (p.Mg / BM) * (p.Ng / BN);
+  const int nkt = (p.Kred + 31) / 32;
+  // Split-K count.  The grid runs in "waves" of resident blocks (CUs x blocks per CU, set by the
+  // ring's LDS: 4 stages x 32 pixels x (BM+BN) bf16 for the 4-wave tiles, 3 stages for the 8-wave
+  // ones, whose 256x256 form is also held to one block per CU by its registers).  For w = 1..4
+  // waves take the largest split count that fits, s_w = floor(w*slots/tiles), and keep the one
+  // with the least w * (ceil(nkt/s_w) + wave_cost) -- k-tiles per block plus its fixed
+  // prologue/epilogue cost.
+  // 1x1 convs (the downsample shortcuts): a k-tile is only 32 pixels x (BM + BN) operand rows while
+  // the epilogue still writes a BM x BN fp32 tile, so blocks need deeper K ranges than the wave
+  // model picks (measured, tools/conv_bench.py: min 24 k-tiles takes the six downsample wgrads from
+  // 0.239 to 0.143 ms at B = 128; the 3x3 shapes keep their optimum at 4; env AVT_WGRAD_MIN_KT_1X1)
+  const int min_kt = (R * S == 1) ? max(k.min_kt, k.min_kt_1x1) : k.min_kt;
+  const bool big = BM == 256 || BN == 256, big2 = BM == 256 && BN == 256;
+  // ring depth: 4 stages (4-wave tiles: two blocks per CU at 128 x 128) / 3 (8-wave); a deeper ring
+  // (AVT_WGRAD_NST / AVT_WGRAD_NST_BIG, or avt_set_wgrad_nst) keeps more k-tiles in flight for a
+  // block alone on its CU -- the small-batch regime, where a block's k range is short and its DMA
+  // latency is exposed (one stage = 32 pixels x (BM + BN) bf16).  The 256 x 128 8-wave tile always
+  // runs the 3-stage ring: nst_big is the 256 x 256 tile's.  nst_knob, the knob's value, feeds the occupancy model and
+  // the kg rule; pl.nst is the ring of the instantiation launched, the nearest at or below it: they differ for knob
+  // values 5 and 7 (launched 4 and 6) and for whatever an environment variable sets outside the setter's range.
+  const int nst_knob = big2 ? k.nst_big : big ? 3 : k.nst;
+  int splits;
+  if (k.blocks > 0) {
+    splits = k.blocks / pl.tiles;
+  } else {
+    int occ = max(1, 163840 / (nst_knob * 64 * (BM + BN)));
+    if (big2) occ = 1;
+    // The share of the chip's block slots the model assumes the wgrad has: with both trunks' backward on two streams a
+    // wgrad shares the chip with the other trunk's kernels, and fewer splits mean fewer partials through the slab and
+    // a shorter reduce.  Auto (default): 65 % for a batch of <= 32, 75 % for <= 64, else 100 % -- measured same-box
+    // (profiles/r6_ab_wgrad_slots*.txt): 65 % is +3.3 % at B=32, 75 % +0.7 % at B=64, and 50 % -1.8 % at B=128.
+    // AVT_WGRAD_SLOTS_PCT / avt_set_wgrad_slots_pct fix it (1-100; 0 = auto).
+    const int slots_pct = k.slots_pct > 0 ? min(k.slots_pct, 100) : N <= 32 ? 65 : N <= 64 ? 75 : 100;
+    const long long slots = max(1LL, (long long)num_cus() * occ * slots_pct / 100);
+    long long best = -1;
+    splits = 1;
+    for (int w = 1; w <= 4; ++w) {
+      const int s_w = (int)(w * slots / pl.tiles);
+      if (s_w < 1) continue;
+      const int kps_w = max(min_kt, (nkt + s_w - 1) / s_w);
+      const long long waves = (((long long)pl.tiles * ((nkt + kps_w - 1) / kps_w)) + slots - 1) / slots;
+      const long long cost = waves * (kps_w + k.wave_cost);
+      if (best < 0 || cost < best) {
+        best = cost;
+        splits = s_w;
+      }
+    }
+  }
+  if (splits < 1) splits = 1;
+  int kps = (nkt + splits - 1) / splits;
+  if (kps < min_kt) kps = min_kt;
+  pl.splits = (nkt + kps - 1) / kps;
+  // two wave groups per block (AVT_WGRAD_KG, default 2): the pairs of blocks the plan puts on one CU
+  // become one 8-wave block over both k ranges with ONE partial tile -- half the split-K slab bytes
+  // (or atomics) at the same waves per CU; 4-wave tiles on the 4-stage ring (2 x 64 KB of LDS at 128 x 128)
+  pl.kg = 1;
+  const int pair_occ = 163840 / (nst_knob * 64 * (BM + BN));  // 4-wave blocks per CU (2 at 128 x 128)
+  // (3x3 only: the 1x1 shortcuts' deep k ranges lost 25-30 % at B = 128 as pairs)
+  if (k.kg >= 2 && pipe && !big && nst_knob == 4 && pair_occ == 2 && pl.splits >= 2 && R * S > 1) {
+    pl.kg = 2;
+    kps *= 2;
+    pl.splits = (nkt + kps - 1) / kps;
+  }
+  p.kt_per_split = pl.kt_per_split = kps;
+  pl.family = pipe ? WG_GATHER : WG_REG;
+  pl.wm = BM == 256 ? 4 : 2; pl.wn = 2; pl.tm = BM == 64 ? 1 : 2; pl.tn = BN / 64;
+  pl.nst = !pipe ? 2 : big2 ? (nst_knob >= 5 ? 5 : nst_knob == 4 ? 4 : 3) : big ? 3
+           : pl.kg == 2 ? 4 : nst_knob >= 8 ? 8 : nst_knob >= 6 ? 6 : 4;
+  // the base ring's instantiations have the fused-reduce (FUSED) and pixel-table (TAB) forms; the deeper-ring A/B
+  // variants keep the separate reduce and the in-loop arithmetic
+  const bool base_ring = pipe && pl.nst == (big ? 3 : 4);
+  pl.tab = base_ring && pixtab_geometry_ok(N, s.H, s.W, R, S, s.stride, s.pad);
+  // slab + reduce pass for moderate split counts (measured faster on layer3/4); very deep splits
+  // (layer1/2: 100-200 splits of a small output) keep the fp32 atomics, which overlap the compute
+  // (the slab holds whole tiles in register order: splits x Mg x Ng, conv_tn_pipe.h)
+  const size_t want = (pipe && pl.splits > 1 && pl.splits <= k.slab_max) ? (size_t)pl.splits * p.Mg * p.Ng * sizeof(float) : 0;
+  pl.slab_bytes = ws.bytes >= want ? want : 0; pl.partials = WG_ATOMICS;
+  if (pl.slab_bytes == 0) return;
+  if (base_ring && k.fused && ws.tickets >= pl.tiles && (long long)(pl.splits - 1) * BM * BN * 4 <= k.fused_max_bytes) {
+    pl.partials = WG_SLAB_FUSED;  // the last block of each tile sums the tile's partials
+    pl.tickets = pl.tiles;
+    return;
+  }
+  // G waves per 64 slab positions: 1 where the positions alone give ~64 K threads, else up to min(splits, 16)
+  const long long positions = (long long)pl.tiles * pl.wm * pl.wn * pl.tm * pl.tn * 4 * 64;
+  pl.G = 1;
+  while (pl.G * 2 <= pl.splits && pl.G * 2 <= 16 && positions * pl.G < 65536) pl.G *= 2;
+  pl.partials = (ws.defer && pl.G == 1) ? WG_SLAB_DEFER : WG_SLAB_REDUCE;  // deferred: the batched reduce's order is G = 1's
+  if (pl.partials == WG_SLAB_DEFER) return;
+  const int nwb = pl.G > 4 ? pl.G : 4, ngrp = nwb / pl.G;
+  pl.red_grid = (int)max(1LL, min(4096LL, (positions + 64LL * ngrp - 1) / (64LL * ngrp)));
+  pl.red_block = nwb * 64;
+}
+
+static WgPlan plan_wgrad(const WgShape& s, const WgWs& ws) {
+  const WgKnobs k = wgrad_knobs();
+  WgPlan pl{};
+  if (!plan_wgrad_stem(pl, s, k, ws) && !plan_wgrad_halo(pl, s, k, ws)) plan_wgrad_gemm(pl, s, k, ws);
   return pl;
 }
 
-static void launch_wgrad_halo(WgradHaloPlan& pl, const bf16_t* x, const bf16_t* dy, float* dw, float* slab,
-                              hipStream_t st) {
-  WgradHaloArgs& a = pl.a;
-  a.x = x;
-  a.dy = dy;
-  a.dw = dw;
-  a.slab = slab;
-  const int BM = pl.WM * pl.RW;
-  const int grid = (a.K / BM) * (a.C / 64) * (pl.row3 ? 3 : 1) * a.splits;
-  if (pl.row3 && pl.WM == 2 && pl.kg == 2)
-    hipLaunchKernelGGL((conv_wgrad_halo_kernel<2, 4, kRow3PrMax, 64, true, 2>), dim3(grid), dim3(512), 0, st, a);
-  else if (pl.row3 && pl.WM == 2)
-    hipLaunchKernelGGL((conv_wgrad_halo_kernel<2, 4, kRow3PrMax, 64, true>), dim3(grid), dim3(256), 0, st, a);
-  else if (pl.row3 && pl.kg == 4)
-    hipLaunchKernelGGL((conv_wgrad_halo_kernel<1, 4, kRow3PrMax, 64, true, 4>), dim3(grid), dim3(512), 0, st, a);
-  else if (pl.row3 && pl.kg == 2 && row3_pf())
-    hipLaunchKernelGGL((conv_wgrad_halo_kernel<1, 4, kRow3PrMax, 64, true, 2, true>), dim3(grid), dim3(256), 0, st, a);
-  else if (pl.row3 && pl.kg == 2)
-    hipLaunchKernelGGL((conv_wgrad_halo_kernel<1, 4, kRow3PrMax, 64, true, 2>), dim3(grid), dim3(256), 0, st, a);
-  else if (pl.row3)
-    hipLaunchKernelGGL((conv_wgrad_halo_kernel<1, 4, kRow3PrMax, 64, true>), dim3(grid), dim3(128), 0, st, a);
-  else if (pl.RW == 32)
-    hipLaunchKernelGGL((conv_wgrad_halo_kernel<2, 6, 72, 32>), dim3(grid), dim3(256), 0, st, a);
-  else if (pl.WM == 2)
-    hipLaunchKernelGGL((conv_wgrad_halo_kernel<2, 5, 160>), dim3(grid), dim3(256), 0, st, a);
-  else
-    hipLaunchKernelGGL((conv_wgrad_halo_kernel<1, 6, 72>), dim3(grid), dim3(128), 0, st, a);
-  if (slab) {  // ordered: groups of per_group splits, then the group heads
-    const long long n = (long long)a.K * 9 * a.C;
-    const unsigned gx = (unsigned)((n / 4 + 255) / 256), gx64 = (unsigned)((n / 4 + 63) / 64);
-    if (pl.groups > 1)
-      hipLaunchKernelGGL(wgrad_halo_reduce_kernel, dim3(gx, (unsigned)pl.groups), dim3(256), 0, st, slab, a.splits, 1,
-                         pl.per_group, n, dw);
-    // the final pass is latency-bound (one thread per 4 outputs, a serial chain of entries): 64-thread blocks
-    hipLaunchKernelGGL(wgrad_halo_reduce_kernel, dim3(gx64, 1), dim3(64), 0, st, slab, pl.groups > 1 ? pl.groups : a.splits,
-                       pl.groups > 1 ? pl.per_group : 1, pl.groups > 1 ? pl.groups : a.splits, n, dw);
+// Launches a plan.  Every wgrad kernel and reduce instantiation is named here, once.  dry: the same table walk, nothing
+// launched (avt_conv_wgrad_plan).  False: no such instantiation.
+static bool launch_wgrad(const WgPlan& pl, const bf16_t* x, const bf16_t* dy, float* dw, void* workspace, int* tickets,
+                         avt_slab_reduce_desc* defer, hipStream_t st, bool dry = false) {
+  float* slab = pl.slab_bytes > 0 ? (float*)workspace : nullptr;
+  const dim3 grid(pl.tiles * pl.splits);
+  const auto tile = [&pl](int wm, int wn, int tm, int tn) { return pl.wm == wm && pl.wn == wn && pl.tm == tm && pl.tn == tn; };
+  bool found = false;
+#define AVT_LAUNCH(KERNEL, GRID, BLOCK, LDS, ...)                                 \
+  {                                                                               \
+    if (!dry) hipLaunchKernelGGL(KERNEL, GRID, dim3(BLOCK), LDS, st, __VA_ARGS__); \
+    found = true;                                                                 \
   }
+  switch (pl.family) {
+    case WG_STEM: {
+      StemWgradArgs a = pl.sa;
+      a.x = x; a.dy = dy; a.slab = slab;
+#define AVT_WSTEM(C) \
+  if (pl.wm == StemWgradCfg<C>::NW) AVT_LAUNCH(conv_stem_wgrad_kernel<C>, dim3(pl.splits), pl.wm * 64, stem_wgrad_lds_bytes<C>(), a)
+      AVT_WSTEM(4)
+      AVT_WSTEM(1)
+#undef AVT_WSTEM
+      if (found)
+        AVT_LAUNCH(stem_wgrad_reduce_kernel, dim3(pl.red_grid), pl.red_block, 0, (const float*)slab, pl.splits,
+                   64 * 49 * a.Creal, dw)
+      return found;
+    }
+    case WG_HALO9:
+    case WG_ROW3: {
+      WgradHaloArgs a = pl.ha;
+      a.x = x; a.dy = dy; a.dw = dw; a.slab = slab;
+#define AVT_WHALO(WM, NST, PRMAX, RW, ROW3, KG, PF)                                                               \
+  if (pl.wm == WM && pl.nst == NST && pl.prmax == PRMAX && pl.rw == RW && (pl.family == WG_ROW3) == ROW3 &&      \
+      pl.kg == KG && (pl.pf != 0) == PF)                                                                          \
+    AVT_LAUNCH((conv_wgrad_halo_kernel<WM, NST, PRMAX, RW, ROW3, KG, PF>), grid, WM * 2 * KG * 64, 0, a)
+      AVT_WHALO(2, 4, kRow3PrMax, 64, true, 2, false)
+      AVT_WHALO(2, 4, kRow3PrMax, 64, true, 1, false)
+      AVT_WHALO(1, 4, kRow3PrMax, 64, true, 4, false)
+      AVT_WHALO(1, 4, kRow3PrMax, 64, true, 2, true)
+      AVT_WHALO(1, 4, kRow3PrMax, 64, true, 2, false)
+      AVT_WHALO(1, 4, kRow3PrMax, 64, true, 1, false)
+      AVT_WHALO(2, 6, 72, 32, false, 1, false)   // K = 64: 4 waves of 32 x 288
+      AVT_WHALO(2, 5, 160, 64, false, 1, false)
+      AVT_WHALO(1, 6, 72, 64, false, 1, false)
+#undef AVT_WHALO
+      if (found && slab != nullptr) {  // ordered: groups of per_group splits, then the group heads
+        const long long n = (long long)a.K * 9 * a.C;
+        const bool two = pl.groups > 1;
+        if (two)
+          AVT_LAUNCH(wgrad_halo_reduce_kernel, dim3((unsigned)((n / 4 + 255) / 256), (unsigned)pl.groups), 256, 0, slab,
+                     a.splits, 1, pl.per_group, n, dw)
+        AVT_LAUNCH(wgrad_halo_reduce_kernel, dim3(pl.red_grid, 1), pl.red_block, 0, slab, two ? pl.groups : a.splits,
+                   two ? pl.per_group : 1, two ? pl.groups : a.splits, n, dw)
+      }
+      return found;
+    }
+    case WG_REG: {
+      GemmTNParams p = pl.g;
+      p.x = x; p.dy = dy; p.dw = dw;
+      const int cvec = p.Cp % 8 == 0 ? 8 : p.Cp;
+#define AVT_TNREG(CVEC, BM, BN) \
+  if (cvec == CVEC && tile(2, 2, BM / 64, BN / 64)) AVT_LAUNCH((gemm_tn_kernel<CVEC, BM, BN>), dim3(pl.tiles, pl.splits), 256, 0, p)
+      AVT_TNREG(4, 128, 128)
+      AVT_TNREG(4, 64, 128)
+      AVT_TNREG(1, 64, 128)
+      AVT_TNREG(1, 64, 64)
+      AVT_TNREG(8, 128, 128)
+      AVT_TNREG(8, 64, 128)
+      AVT_TNREG(8, 128, 64)
+      AVT_TNREG(8, 64, 64)
+#undef AVT_TNREG
+      return found;
+    }
+    case WG_GATHER: {
+      GemmTNPipeParams pp;
+      GemmTNParams& p = pp.p = pl.g;
+      p.x = x; p.dy = dy; p.dw = dw;
+      pp.div_pq = make_magic((unsigned)(p.P * p.Q));
+      pp.div_q = make_magic((unsigned)p.Q);
+      pp.dy_bytes = (unsigned)((size_t)p.Kred * p.Mg * 2);
+      pp.x_bytes = (unsigned)((size_t)(p.Kred / (p.P * p.Q)) * p.H * p.W * p.Cp * 2);
+      pp.slab = slab; pp.slab_bytes = (unsigned)pl.slab_bytes; pp.splits = pl.splits;
+      pp.cnt = pl.partials == WG_SLAB_FUSED ? tickets : nullptr;
+      // the registered per-pixel table of this geometry: per device and stateful, so looked up here
+      pp.tab = pl.tab && !dry ? pixtab_lookup(p.Kred / (p.P * p.Q), p.H, p.W, p.Cp, p.R, p.S, p.stride, p.pad) : nullptr;
+      const bool fused = pl.partials == WG_SLAB_FUSED, tab = pp.tab != nullptr;
+#define AVT_TN(WM, WN, TM, TN, NST, KG, FUSED, TAB)                                     \
+  if (tile(WM, WN, TM, TN) && pl.nst == NST && pl.kg == KG && fused == FUSED && tab == TAB) \
+    AVT_LAUNCH((conv_tn_pipe_kernel<WM, WN, TM, TN, NST, KG, FUSED, TAB>), grid, WM * WN * 64 * KG, 0, pp)
+#define AVT_TN4(WM, WN, TM, TN, NST, KG) /* a base-ring tile: plain, FUSED, TAB, both */ \
+  AVT_TN(WM, WN, TM, TN, NST, KG, false, false)                                          \
+  AVT_TN(WM, WN, TM, TN, NST, KG, true, false)                                           \
+  AVT_TN(WM, WN, TM, TN, NST, KG, false, true)                                           \
+  AVT_TN(WM, WN, TM, TN, NST, KG, true, true)
+#define AVT_TN_4WAVE(TM, TN) /* a 4-wave tile: the 4-stage ring alone and as a pair of k groups, the deeper rings */ \
+  AVT_TN4(2, 2, TM, TN, 4, 1)                                                                                         \
+  AVT_TN4(2, 2, TM, TN, 4, 2)                                                                                         \
+  AVT_TN(2, 2, TM, TN, 6, 1, false, false)                                                                            \
+  AVT_TN(2, 2, TM, TN, 8, 1, false, false)
+      AVT_TN4(4, 2, 2, 4, 3, 1)  // 256 x 256
+      AVT_TN(4, 2, 2, 4, 4, 1, false, false)
+      AVT_TN(4, 2, 2, 4, 5, 1, false, false)
+      AVT_TN4(4, 2, 2, 2, 3, 1)  // 256 x 128
+      AVT_TN_4WAVE(2, 2)
+      AVT_TN_4WAVE(1, 2)
+      AVT_TN_4WAVE(2, 1)
+      AVT_TN_4WAVE(1, 1)
+#undef AVT_TN_4WAVE
+#undef AVT_TN4
+#undef AVT_TN
+      if (!found || pl.partials == WG_ATOMICS || pl.partials == WG_SLAB_FUSED) return found;
+      if (!dry && diag_skip(4, st)) return true;
+      if (pl.partials == WG_SLAB_DEFER) {  // left for the batched reduce
+        if (!dry) *defer = avt_slab_reduce_desc{slab, dw, pl.splits, pl.tiles, p.Ng / (pl.wn * pl.tn * 32), p.Mg,
+                                                p.R * p.S * p.Creal, pl.wm, pl.wn, pl.tm, pl.tn};
+        return true;
+      }
+      found = false;
+#define AVT_RED(WM, WN, TM, TN)                                                                                       \
+  if (tile(WM, WN, TM, TN))                                                                                           \
+    AVT_LAUNCH((wgrad_slab_reduce_native_kernel<WM, WN, TM, TN>), dim3(pl.red_grid), pl.red_block, 0, slab, pl.splits, \
+               pl.tiles, p.Ng / (WN * TN * 32), p.Mg, p.R * p.S * p.Creal, pl.G, dw)
+      AVT_RED(4, 2, 2, 4)
+      AVT_RED(4, 2, 2, 2)
+      AVT_RED(2, 2, 2, 2)
+      AVT_RED(2, 2, 2, 1)
+      AVT_RED(2, 2, 1, 2)
+      AVT_RED(2, 2, 1, 1)
+#undef AVT_RED
+      return found;
+    }
+  }
+#undef AVT_LAUNCH
+  return false;
 }
 
 extern "C" int avt_set_halo_tps2(int on) {
@@ -2231,48 +2333,6 @@ extern "C" int avt_set_wgrad_halo(int on) {
   return AVT_OK;
 }
 
-namespace avt {
-// stem wgrad on conv_stem_wgrad_kernel: grid (one block per CU at most) and its slab bytes; grid 0 = n/a
-struct StemWgradPlan {
-  int grid = 0;
-  size_t slab_bytes = 0;
-  StemWgradArgs a{};
-};
-static StemWgradPlan stem_wgrad_plan(int N, int H, int W, int Cp, int Creal, int K, int R, int S, int stride, int pad) {
-  StemWgradPlan pl;
-  if (!((Cp == 4 || Cp == 1) && stem_wgrad_enabled() && K == 64 && R == 7 && S == 7 && stride == 2 && pad == 3 &&
-        Creal >= 1 && Creal <= Cp && N >= 1))
-    return pl;
-  const int OH = (H + 2 * pad - R) / stride + 1, OW = (W + 2 * pad - S) / stride + 1;
-  if (OH < 1 || OW < 1) return pl;
-  if ((size_t)N * H * W * Cp * 2 >= (1ull << 31) || (size_t)N * OH * OW * 64 * 2 >= (1ull << 31)) return pl;  // 32-bit offsets
-  pl.a.N = N; pl.a.IH = H; pl.a.IW = W; pl.a.OH = OH; pl.a.OW = OW; pl.a.Creal = Creal;
-  pl.a.tiles_per_row = (OW + 31) / 32;
-  pl.a.total_tiles = N * OH * pl.a.tiles_per_row;
-  const int nw = Cp == 4 ? StemWgradCfg<4>::NW : StemWgradCfg<1>::NW;
-  const int blocks = (pl.a.total_tiles + nw - 1) / nw;
-  pl.grid = blocks < num_cus() ? blocks : num_cus();
-  pl.slab_bytes = (size_t)pl.grid * 64 * 49 * Creal * sizeof(float);
-  return pl;
-}
-}  // namespace avt
-
-// A/B knob: the fused slab reduce (conv_tn_pipe.h FUSED) for the tap-gather wgrads, avt_set_wgrad_fused / env
-// AVT_WGRAD_FUSED (0 default = the separate reduce launch; 1 = fused up to g_wgrad_fused_max_bytes of other splits'
-// partials per tile).  Bitwise equal where the separate reduce runs one wave per position, but SLOWER: the wgrad
-// family 355 -> 214 TF/s, the step -7 % at B=32 and -1.7 % at B=128 (profiles/r6_ab_wgrad_fused.txt) -- the
-// write-through partials and the last block's serial read of the other splits cost more than the reduce launch
-static int g_wgrad_fused = -1;
-static long long g_wgrad_fused_max_bytes = -1;
-static bool wgrad_fused_plan(const WgradPlan& pl) {
-  if (g_wgrad_fused < 0) g_wgrad_fused = getenv("AVT_WGRAD_FUSED") ? atoi(getenv("AVT_WGRAD_FUSED")) : 0;
-  if (g_wgrad_fused_max_bytes < 0)
-    g_wgrad_fused_max_bytes = getenv("AVT_WGRAD_FUSED_MAX_KB") ? 1024LL * atoll(getenv("AVT_WGRAD_FUSED_MAX_KB"))
-                                                               : 2048LL * 1024;
-  return g_wgrad_fused && pl.slab_bytes > 0 && tn_fusable(pl) &&
-         (long long)(pl.splits - 1) * pl.BM * pl.BN * 4 <= g_wgrad_fused_max_bytes;
-}
-
 extern "C" int avt_set_wgrad_fused(int on, int max_kb) {
   AVT_REQUIRE(on >= -1 && on <= 1, "avt_set_wgrad_fused: %d (0 separate reduce, 1 fused, -1 env AVT_WGRAD_FUSED)", on);
   AVT_REQUIRE(max_kb >= -1, "avt_set_wgrad_fused: max_kb=%d", max_kb);
@@ -2281,31 +2341,51 @@ extern "C" int avt_set_wgrad_fused(int on, int max_kb) {
   return AVT_OK;
 }
 
+// what every wgrad entry point and avt_conv_wgrad_plan refuse
+static int wgrad_check_shape(const WgShape& s) {
+  AVT_REQUIRE(s.K % 64 == 0, "conv2d_wgrad: K=%d must be a multiple of 64", s.K);
+  AVT_REQUIRE(s.Cp % 8 == 0 || s.Cp == 4 || s.Cp == 1, "conv2d_wgrad: C=%d unsupported", s.Cp);
+  AVT_REQUIRE(s.Creal <= s.Cp, "conv2d_wgrad: Creal > Cp");
+  AVT_REQUIRE(s.Cp % 8 != 0 || s.Creal == s.Cp, "conv2d_wgrad: channel padding only for the stems");
+  return AVT_OK;
+}
+
+// the two size queries plan for a caller who brings what they size
+static const WgWs kWsAnySlab{~(size_t)0, 0, false}, kWsAnyTickets{~(size_t)0, 1 << 30, false};
+
 // tickets the fused wgrad slab reduce needs for this conv (avt_conv2d_wgrad_tk), 0: the shape does not use it
 extern "C" int avt_conv2d_wgrad_tickets(int N, int H, int W, int Cp, int Creal, int K, int R, int S, int stride,
                                         int pad) {
-  using namespace avt;
-  if (stem_wgrad_plan(N, H, W, Cp, Creal, K, R, S, stride, pad).grid > 0) return 0;
-  if (wgrad_halo_plan(N, H, W, Cp, Creal, K, R, S, stride, pad).ok) return 0;
-  const WgradPlan pl = wgrad_plan(N, H, W, Cp, Creal, K, R, S, stride, pad);
-  return wgrad_fused_plan(pl) ? pl.tiles : 0;
+  return plan_wgrad(WgShape{N, H, W, Cp, Creal, K, R, S, stride, pad}, kWsAnyTickets).tickets;
 }
 
 extern "C" size_t avt_conv2d_wgrad_workspace(int N, int H, int W, int Cp, int Creal, int K, int R, int S, int stride,
                                              int pad) {
-  const StemWgradPlan sp = stem_wgrad_plan(N, H, W, Cp, Creal, K, R, S, stride, pad);
-  if (sp.grid > 0) return sp.slab_bytes;
-  const WgradHaloPlan hp = wgrad_halo_plan(N, H, W, Cp, Creal, K, R, S, stride, pad);
-  if (hp.ok) return hp.slab_bytes;
-  return wgrad_plan(N, H, W, Cp, Creal, K, R, S, stride, pad).slab_bytes;
+  return plan_wgrad(WgShape{N, H, W, Cp, Creal, K, R, S, stride, pad}, kWsAnySlab).slab_bytes;
+}
+
+static int conv2d_wgrad_impl(const void* x, const void* dy, float* dw, const WgShape& s, void* workspace,
+                             size_t ws_bytes, int* tickets, int n_tickets, avt_slab_reduce_desc* defer, void* stream) {
+  AVT_REQUIRE(x && dy && dw, "conv2d_wgrad: null pointer");
+  if (const int rc = wgrad_check_shape(s)) return rc;
+  const WgPlan pl = plan_wgrad(s, WgWs{workspace ? ws_bytes : 0, tickets ? n_tickets : 0, defer != nullptr});
+  AVT_REQUIRE(launch_wgrad(pl, (const bf16_t*)x, (const bf16_t*)dy, dw, workspace, tickets, defer, (hipStream_t)stream),
+              "conv2d_wgrad: no kernel for the plan");
+  return check_launch(pl.family == WG_STEM ? "conv2d_wgrad(stem)"
+                      : pl.family == WG_HALO9 || pl.family == WG_ROW3 ? "conv2d_wgrad(halo)" : "conv2d_wgrad");
 }
 
 // dw += wgrad.  With a workspace of avt_conv2d_wgrad_workspace() bytes the split-K partials go
 // through an fp32 slab + one reduction pass (deterministic, 2x cheaper than atomics); without it
 // (or for the stems) they are added with fp32 atomics.  dw must hold zero or a gradient to add to.
+// tickets: >= avt_conv2d_wgrad_tickets() ints, zero on entry (the kernel leaves them zero), or null: the split-K slab
+// is summed by the last block of each tile instead of a separate reduce launch (same bits)
 extern "C" int avt_conv2d_wgrad_tk(const void* x, const void* dy, float* dw, int N, int H, int W, int Cp, int Creal,
                                    int K, int R, int S, int stride, int pad, void* workspace, size_t ws_bytes,
-                                   int* tickets, int n_tickets, void* stream);
+                                   int* tickets, int n_tickets, void* stream) {
+  return conv2d_wgrad_impl(x, dy, dw, WgShape{N, H, W, Cp, Creal, K, R, S, stride, pad}, workspace, ws_bytes, tickets,
+                           n_tickets, nullptr, stream);
+}
 
 extern "C" int avt_conv2d_wgrad(const void* x, const void* dy, float* dw, int N, int H, int W, int Cp, int Creal,
                                 int K, int R, int S, int stride, int pad, void* workspace, size_t ws_bytes,
@@ -2314,26 +2394,38 @@ extern "C" int avt_conv2d_wgrad(const void* x, const void* dy, float* dw, int N,
                              stream);
 }
 
-// tickets: >= avt_conv2d_wgrad_tickets() ints, zero on entry (the kernel leaves them zero), or null: the split-K slab
-// is summed by the last block of each tile instead of a separate reduce launch (same bits)
-static int conv2d_wgrad_impl(const void* x, const void* dy, float* dw, int N, int H, int W, int Cp, int Creal, int K,
-                             int R, int S, int stride, int pad, void* workspace, size_t ws_bytes, int* tickets,
-                             int n_tickets, avt_slab_reduce_desc* defer, void* stream);
-
-extern "C" int avt_conv2d_wgrad_tk(const void* x, const void* dy, float* dw, int N, int H, int W, int Cp, int Creal,
-                                   int K, int R, int S, int stride, int pad, void* workspace, size_t ws_bytes,
-                                   int* tickets, int n_tickets, void* stream) {
-  return conv2d_wgrad_impl(x, dy, dw, N, H, W, Cp, Creal, K, R, S, stride, pad, workspace, ws_bytes, tickets,
-                           n_tickets, nullptr, stream);
-}
-
 extern "C" int avt_conv2d_wgrad_defer(const void* x, const void* dy, float* dw, int N, int H, int W, int Cp, int Creal,
                                       int K, int R, int S, int stride, int pad, void* workspace, size_t ws_bytes,
                                       avt_slab_reduce_desc* desc, void* stream) {
   AVT_REQUIRE(desc, "conv2d_wgrad_defer: null descriptor");
   desc->splits = 0;
-  return conv2d_wgrad_impl(x, dy, dw, N, H, W, Cp, Creal, K, R, S, stride, pad, workspace, ws_bytes, nullptr, 0, desc,
-                           stream);
+  return conv2d_wgrad_impl(x, dy, dw, WgShape{N, H, W, Cp, Creal, K, R, S, stride, pad}, workspace, ws_bytes, nullptr,
+                           0, desc, stream);
+}
+
+// The plan of a wgrad call, from its shape, the current knobs and what the caller brings (include/avt_tuning.h): no
+// GPU, no launch.
+extern "C" int avt_conv_wgrad_plan(int N, int H, int W, int Cp, int Creal, int K, int R, int S, int stride, int pad,
+                                   int ws_mode, int* plan) {
+  AVT_REQUIRE(plan, "conv_wgrad_plan: null pointer");
+  AVT_REQUIRE(ws_mode >= 0 && ws_mode <= 3,
+              "conv_wgrad_plan: ws_mode=%d (0 no workspace, 1 the workspace, 2 with tickets, 3 with a defer descriptor)", ws_mode);
+  const WgShape s{N, H, W, Cp, Creal, K, R, S, stride, pad};
+  if (const int rc = wgrad_check_shape(s)) return rc;
+  AVT_REQUIRE(N >= 1 && H >= 1 && W >= 1 && Cp >= 1 && Creal >= 1 && K >= 64 && R >= 1 && S >= 1 && pad >= 0 &&
+                  (stride == 1 || stride == 2) && H + 2 * pad >= R && W + 2 * pad >= S,
+              "conv_wgrad_plan: empty input, taps or output, negative padding, or a stride other than 1 and 2");
+  WgWs ws{0, 0, ws_mode == 3};
+  if (ws_mode >= 1) ws.bytes = plan_wgrad(s, kWsAnySlab).slab_bytes;
+  if (ws_mode == 2) ws.tickets = plan_wgrad(s, kWsAnyTickets).tickets;
+  const WgPlan pl = plan_wgrad(s, ws);
+  const bool found = launch_wgrad(pl, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, true);
+  const int out[AVT_WGRAD_PLAN_INTS] = {pl.family, pl.wm, pl.wn, pl.tm, pl.tn, pl.rw, pl.prmax, pl.nst, pl.kg, pl.pf,
+                                        pl.tab, pl.splits, pl.kt_per_split, pl.tiles, pl.partials,
+                                        (int)(pl.slab_bytes & 0x7fffffff), (int)(pl.slab_bytes >> 31), pl.tickets,
+                                        pl.G, pl.red_grid, pl.red_block, pl.groups, pl.per_group, found ? 1 : 0};
+  for (int i = 0; i < AVT_WGRAD_PLAN_INTS; ++i) plan[i] = out[i];
+  return AVT_OK;
 }
 
 extern "C" int avt_wgrad_reduce_batch(const avt_slab_reduce_desc* descs, int n, void* stream) {
@@ -2360,103 +2452,3 @@ extern "C" int avt_wgrad_reduce_batch(const avt_slab_reduce_desc* descs, int n, 
   return check_launch("wgrad_reduce_batch");
 }
 
-static int conv2d_wgrad_impl(const void* x, const void* dy, float* dw, int N, int H, int W, int Cp, int Creal, int K,
-                             int R, int S, int stride, int pad, void* workspace, size_t ws_bytes, int* tickets,
-                             int n_tickets, avt_slab_reduce_desc* defer, void* stream) {
-  AVT_REQUIRE(x && dy && dw, "conv2d_wgrad: null pointer");
-  AVT_REQUIRE(K % 64 == 0, "conv2d_wgrad: K=%d must be a multiple of 64", K);
-  AVT_REQUIRE(Cp % 8 == 0 || Cp == 4 || Cp == 1, "conv2d_wgrad: C=%d unsupported", Cp);
-  AVT_REQUIRE(Creal <= Cp, "conv2d_wgrad: Creal > Cp");
-  AVT_REQUIRE(Cp % 8 != 0 || Creal == Cp, "conv2d_wgrad: channel padding only for the stems");
-  StemWgradPlan sp = stem_wgrad_plan(N, H, W, Cp, Creal, K, R, S, stride, pad);
-  if (sp.grid > 0 && workspace != nullptr && ws_bytes >= sp.slab_bytes) {
-    sp.a.x = (const bf16_t*)x;
-    sp.a.dy = (const bf16_t*)dy;
-    sp.a.slab = (float*)workspace;
-    sp.a.x_bytes = (unsigned)((size_t)N * H * W * Cp * 2);
-    sp.a.dy_bytes = (unsigned)((size_t)N * sp.a.OH * sp.a.OW * 64 * 2);
-    hipStream_t st = (hipStream_t)stream;
-    if (Cp == 4)
-      hipLaunchKernelGGL(conv_stem_wgrad_kernel<4>, dim3(sp.grid), dim3(StemWgradCfg<4>::NW * 64),
-                         stem_wgrad_lds_bytes<4>(), st, sp.a);
-    else
-      hipLaunchKernelGGL(conv_stem_wgrad_kernel<1>, dim3(sp.grid), dim3(StemWgradCfg<1>::NW * 64),
-                         stem_wgrad_lds_bytes<1>(), st, sp.a);
-    const int n = 64 * 49 * Creal;
-    hipLaunchKernelGGL(stem_wgrad_reduce_kernel, dim3((n + 63) / 64), dim3(1024), 0, st, (const float*)workspace,
-                       sp.grid, n, dw);
-    return check_launch("conv2d_wgrad(stem)");
-  }
-  WgradHaloPlan hp = wgrad_halo_plan(N, H, W, Cp, Creal, K, R, S, stride, pad);
-  if (hp.ok) {
-    // without the workspace the split partials are added with fp32 atomics
-    float* hslab = (hp.slab_bytes > 0 && workspace != nullptr && ws_bytes >= hp.slab_bytes) ? (float*)workspace : nullptr;
-    launch_wgrad_halo(hp, (const bf16_t*)x, (const bf16_t*)dy, dw, hslab, (hipStream_t)stream);
-    return check_launch("conv2d_wgrad(halo)");
-  }
-  WgradPlan pl = wgrad_plan(N, H, W, Cp, Creal, K, R, S, stride, pad);
-  pl.p.dy = (const bf16_t*)dy;
-  pl.p.x = (const bf16_t*)x;
-  pl.p.dw = dw;
-  float* slab = (pl.slab_bytes > 0 && workspace != nullptr && ws_bytes >= pl.slab_bytes) ? (float*)workspace : nullptr;
-  hipStream_t st = (hipStream_t)stream;
-  const int BM = pl.BM, BN = pl.BN;
-  int* tk = (slab != nullptr && tickets != nullptr && n_tickets >= pl.tiles && Cp % 8 == 0 && wgrad_fused_plan(pl))
-                ? tickets
-                : nullptr;
-  if (Cp == 4) {
-    if (BM == 128) launch_tn<4, 128, 128>(pl, slab, st); else launch_tn<4, 64, 128>(pl, slab, st);
-  } else if (Cp == 1) {
-    if (BN == 128) launch_tn<1, 64, 128>(pl, slab, st); else launch_tn<1, 64, 64>(pl, slab, st);
-  } else if (BM == 256) {
-    if (BN == 256) launch_tn<8, 256, 256>(pl, slab, st, tk);
-    else launch_tn<8, 256, 128>(pl, slab, st, tk);  // the plan pairs BM 256 with BN >= 128 only
-  } else if (BN == 128) {
-    if (BM == 128) launch_tn<8, 128, 128>(pl, slab, st, tk); else launch_tn<8, 64, 128>(pl, slab, st, tk);
-  } else {
-    if (BM == 128) launch_tn<8, 128, 64>(pl, slab, st, tk); else launch_tn<8, 64, 64>(pl, slab, st, tk);
-  }
-  if (slab && tk == nullptr && !diag_skip(4, st)) {
-    // G waves per 64 slab positions: 1 where the positions alone give ~64 K threads, else up to min(splits, 16)
-    const int wm = BM == 256 ? 4 : 2, wn = 2, tm = BM == 64 ? 1 : 2, tn = BN == 256 ? 4 : BN == 128 ? 2 : 1;
-    const long long positions = (long long)pl.tiles * wm * wn * tm * tn * 4 * 64;
-    int G = 1;
-    while (G * 2 <= pl.splits && G * 2 <= 16 && positions * G < 65536) G *= 2;
-    if (defer != nullptr && G == 1) {  // left for the batched reduce (the same order: G = 1)
-      defer->slab = slab;
-      defer->dw = dw;
-      defer->splits = pl.splits;
-      defer->tiles = pl.tiles;
-      defer->nnt = pl.p.Ng / BN;
-      defer->Mg = pl.p.Mg;
-      defer->ldw = R * S * Creal;
-      defer->wm = wm; defer->wn = wn; defer->tm = tm; defer->tn = tn;
-      return check_launch("conv2d_wgrad");
-    }
-    const int nwb = G > 4 ? G : 4, ngrp = nwb / G;
-    long long blocks = (positions + 64LL * ngrp - 1) / (64LL * ngrp);
-    if (blocks > 4096) blocks = 4096;
-    if (blocks < 1) blocks = 1;
-    const int nnt = pl.p.Ng / BN, ldw = R * S * Creal;
-    const dim3 g((unsigned)blocks), b(nwb * 64);
-    if (BM == 256 && BN == 256)
-      hipLaunchKernelGGL((wgrad_slab_reduce_native_kernel<4, 2, 2, 4>), g, b, 0, st, slab, pl.splits, pl.tiles, nnt,
-                         pl.p.Mg, ldw, G, dw);
-    else if (BM == 256)
-      hipLaunchKernelGGL((wgrad_slab_reduce_native_kernel<4, 2, 2, 2>), g, b, 0, st, slab, pl.splits, pl.tiles, nnt,
-                         pl.p.Mg, ldw, G, dw);
-    else if (BM == 128 && BN == 128)
-      hipLaunchKernelGGL((wgrad_slab_reduce_native_kernel<2, 2, 2, 2>), g, b, 0, st, slab, pl.splits, pl.tiles, nnt,
-                         pl.p.Mg, ldw, G, dw);
-    else if (BM == 128)
-      hipLaunchKernelGGL((wgrad_slab_reduce_native_kernel<2, 2, 2, 1>), g, b, 0, st, slab, pl.splits, pl.tiles, nnt,
-                         pl.p.Mg, ldw, G, dw);
-    else if (BN == 128)
-      hipLaunchKernelGGL((wgrad_slab_reduce_native_kernel<2, 2, 1, 2>), g, b, 0, st, slab, pl.splits, pl.tiles, nnt,
-                         pl.p.Mg, ldw, G, dw);
-    else
-      hipLaunchKernelGGL((wgrad_slab_reduce_native_kernel<2, 2, 1, 1>), g, b, 0, st, slab, pl.splits, pl.tiles, nnt,
-                         pl.p.Mg, ldw, G, dw);
-  }
-  return check_launch("conv2d_wgrad");
-}

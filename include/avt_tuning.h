@@ -131,6 +131,34 @@ int avt_set_wgrad_slots_pct(int pct);
 int avt_conv_fwd_plan(int N, int T, int H, int W, int Cp, int K, int KT, int R, int S, int stride, int pad_t, int pad,
                       int epi, int* plan);
 
+/* Which kernels a 2-D weight gradient runs, under the knobs as they stand: a host query (no GPU needed, nothing
+ * launched; without a device the planner assumes 256 CUs).  The shape arguments are avt_conv2d_wgrad's, and it refuses
+ * what avt_conv2d_wgrad refuses.  ws_mode says what the caller brings: 0 = no workspace, 1 = the workspace
+ * avt_conv2d_wgrad_workspace sizes, 2 = that and the tickets avt_conv2d_wgrad_tickets sizes (avt_conv2d_wgrad_tk),
+ * 3 = that workspace and a descriptor (avt_conv2d_wgrad_defer).  plan[AVT_WGRAD_PLAN_INTS] receives
+ *   [0] family: 0 the 7x7 stem kernel, 1 halo, nine taps per block, 2 halo, one filter row per block (ROW3), 3 tap
+ *       gather (conv_tn_pipe_kernel), 4 register-staged gemm_tn_kernel
+ *   [1..4] WM, WN, TM, TN: waves per block (rows x columns; ROW3: per k group) and 32 x 32 MFMA tiles per wave -- the
+ *       block computes WM*TM*32 x WN*TN*32 outputs (halo: TN = the 32-channel tap subtiles per wave, 9 or 3; stem:
+ *       WM = waves per block, TM = TN = 0)
+ *   [5] halo: output channels per wave (RW)   [6] halo: LDS patch rows (PRMAX)
+ *   [7] LDS ring stages of the instantiation launched (avt_set_wgrad_nst's 5 and 7 launch 4 and 6; register-staged
+ *       and stem: their double buffer, 2)
+ *   [8] k groups per block   [9] ROW3: 1 = the prefetch form
+ *   [10] tap gather: 1 = the launch reads the per-pixel table of the geometry where one is registered
+ *       (avt_wgrad_pixtab_register; the registry is per device, so the query cannot say whether one is)
+ *   [11] split-K count   [12] k-tiles per split   [13] blocks per split -- the grid is [11] x [13] blocks (stem: [11]
+ *       = blocks, each leaving a partial, [12] = 0, [13] = its 32-pixel wave tiles)
+ *   [14] where the partials go: 0 a slab and a separate reduce, 1 a slab summed by the last block of each tile (the
+ *       tickets), 2 a slab left to avt_wgrad_reduce_batch, 3 fp32 atomics straight into dw
+ *   [15] slab bytes, the low 31 bits   [16] slab bytes >> 31   [17] tickets used
+ *   [18] the tap-gather reduce's waves per 64 slab positions (G)   [19], [20] grid and block of the reduce (halo: of
+ *       its last pass)   [21], [22] halo reduce: groups, splits per group
+ *   [23] 1 = the launcher has an instantiation for the plan (0: the call would be refused) */
+#define AVT_WGRAD_PLAN_INTS 24
+int avt_conv_wgrad_plan(int N, int H, int W, int Cp, int Creal, int K, int R, int S, int stride, int pad, int ws_mode,
+                        int* plan);
+
 #ifdef __cplusplus
 }
 #endif
