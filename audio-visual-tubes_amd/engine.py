@@ -11,6 +11,7 @@ from __future__ import annotations
 
 import contextlib
 import os
+import weakref
 from collections import OrderedDict
 from typing import Dict, List, Optional, Tuple
 
@@ -42,6 +43,55 @@ def _numel(shape) -> int:
     for s in shape:
         n *= s
     return n
+
+
+def desc_table(records: List[bytes], bytes_query: Optional[str], dev) -> torch.Tensor:
+    """struct-packed descriptor records -> the device table a batched launch reads.  bytes_query names the library's
+    ``*_desc_bytes`` entry the record size is held against (None: records of a layout already checked)."""
+    assert bytes_query is None or len(records[0]) == int(query(bytes_query))
+    return torch.frombuffer(bytearray(b"".join(records)), dtype=torch.uint8).to(dev)
+
+
+class ParentLink:
+    """Mixin of the trunk modules (model.ResNet, resnet3D.ResNet): the link to the model whose flat store holds the
+    trunk's parameters -- ``_avt_parent`` = (weakref to the owner, the trunk's prefix in its store), or None for a
+    trunk on its own, which keeps a flat store of its own (``_flat_store()``, the module's)."""
+
+    def _adopt(self, parent, prefix: str):
+        """Called by the owning model once its flat store holds this trunk's parameters."""
+        self._avt_parent = (weakref.ref(parent), prefix)
+        self._own_flat = None
+        self._avt_engine = None
+
+    def __getstate__(self):
+        state = self.__dict__.copy()
+        state["_avt_engine"] = None
+        return state
+
+    def _owner(self):
+        """The owning model while it is alive, else None."""
+        return self._avt_parent[0]() if self._avt_parent is not None else None
+
+    def _apply(self, fn, recurse=True):
+        owner = self._owner()
+        if owner is not None:
+            owner._apply(fn)
+            return self
+        self._flat_store().apply(fn)
+        self._avt_engine = None
+        return self
+
+    def _resolve(self):
+        """(the owning model or None, this trunk's prefix in the store, the store); raises for an adopted trunk whose
+        owner is gone or holds another module under its name."""
+        if self._avt_parent is None:
+            return None, "", self._flat_store()
+        owner, prefix = self._owner(), self._avt_parent[1]
+        if owner is None:
+            raise RuntimeError("avt: the AVENet owning this trunk no longer exists")
+        if getattr(owner, prefix.rstrip("."), None) is not self:
+            raise RuntimeError("avt: this trunk is no longer its parent's (a copied trunk; copy the whole model)")
+        return owner, prefix, owner._flat
 
 
 class FlatStore:
@@ -381,9 +431,7 @@ class AVEngine:
             maxel = max(maxel, tmax)
             self._pack_parts[tr.prefix] = (first, len(descs) - first, tmax)
         if descs:  # (an engine of 3-D trunks only packs its own operands, tube.py)
-            assert len(descs[0]) == int(query("avt_pack_desc_bytes"))
-            blob = b"".join(descs)
-            self._pack_table = torch.frombuffer(bytearray(blob), dtype=torch.uint8).to(dev)
+            self._pack_table = desc_table(descs, "avt_pack_desc_bytes", dev)
         self._pack_n, self._pack_max = len(descs), maxel
 
     def head_ws(self, B: int, C: int) -> torch.Tensor:
@@ -435,13 +483,8 @@ class AVEngine:
         self.folds: Dict[str, Tuple[torch.Tensor, torch.Tensor]] = {}
         self._fold_parts = {}  # trunk prefix -> (descriptor table, records, max elements)
         for tr in self.trunks2d:
-            pairs = [(tr.stem, tr.bn1)]
-            for b in tr.blocks:
-                pairs += [(b["conv1"], b["bn1"]), (b["conv2"], b["bn2"])]
-                if b["down"] is not None:
-                    pairs.append((b["down"], b["bnd"]))
             descs, tmax = [], 0
-            for spec, bn in pairs:
+            for spec, bn in tr.conv_bn_pairs():
                 wf = torch.empty(spec.cout, spec.kg, device=dev, dtype=torch.bfloat16)
                 bias = torch.empty((2, spec.cout) if spec.is_stem else (spec.cout,), device=dev, dtype=torch.float32)
                 self.folds[spec.name] = (wf, bias)
@@ -451,9 +494,7 @@ class AVEngine:
                 descs.append(struct.pack("<QQQQQQQiiiiiifi", *[t.data_ptr() for t in ptrs], spec.cout, spec.k * spec.k,
                                          spec.cin, spec.cp, spec.kg, int(spec.is_stem), self.BN_EPS, 0))
                 tmax = max(tmax, spec.cout * spec.kg)
-            assert len(descs[0]) == int(query("avt_fold_desc_bytes"))
-            table = torch.frombuffer(bytearray(b"".join(descs)), dtype=torch.uint8).to(dev)
-            self._fold_parts[tr.prefix] = (table, len(descs), tmax)
+            self._fold_parts[tr.prefix] = (desc_table(descs, "avt_fold_desc_bytes", dev), len(descs), tmax)
 
     def fold_state(self):
         """What the folded operands depend on.  torch's in-place writes to the flat parameter / buffer storage

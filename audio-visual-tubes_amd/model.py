@@ -9,13 +9,12 @@ Parameters.  Compute runs in libavt (HIP, gfx950); there is no CPU path.
 """
 from __future__ import annotations
 
-import weakref
 from typing import Optional
 
 import torch
 from torch import nn
 
-from .engine import AVEngine, FlatStore, trainable
+from .engine import AVEngine, FlatStore, ParentLink, trainable
 
 # ---------------------------------------------------------------------------------------------
 # module shells: exactly the reference's module tree (models/base_models.py:32-69, 113-193)
@@ -36,7 +35,7 @@ class BasicBlock(nn.Module):
         self.stride = stride
 
 
-class ResNet(nn.Module):
+class ResNet(ParentLink, nn.Module):
     """base_models.ResNet(BasicBlock, [2,2,2,2], modal) on libavt.  Inside an AVENet its parameters are
     views of the parent's flat storage; constructed on its own it keeps a flat store of its own.
     ``forward(x)`` (base_models.py:195-213) returns the layer4 map [N,512,h,w] fp32 with gradients
@@ -81,9 +80,7 @@ class ResNet(nn.Module):
         return self
 
     def _eval_backward(self) -> bool:
-        if self._avt_parent is not None and self._avt_parent[0]() is not None:
-            return bool(getattr(self._avt_parent[0](), "_avt_eval_backward", False))
-        return bool(getattr(self, "_avt_eval_backward", False))
+        return bool(getattr(self._resolve()[0] or self, "_avt_eval_backward", False))
 
     def _make_layer(self, planes, blocks, stride):
         downsample = None
@@ -102,45 +99,18 @@ class ResNet(nn.Module):
             return False
         return name != ("conv1.weight" if self.modal == "audio" else "conv1_a.weight")
 
-    def __getstate__(self):
-        state = self.__dict__.copy()
-        state["_avt_engine"] = None
-        return state
-
-    def _adopt(self, parent, prefix: str):
-        """Called by the owning AVENet once its flat store holds this trunk's parameters."""
-        self._avt_parent = (weakref.ref(parent), prefix)
-        self._own_flat = None
-        self._avt_engine = None
-
     def _flat_store(self) -> FlatStore:
         if self._own_flat is None:
             self._own_flat = FlatStore(self, lambda n, s=self: s._trainable(n))
         return self._own_flat
 
-    def _apply(self, fn, recurse=True):
-        if self._avt_parent is not None and self._avt_parent[0]() is not None:
-            self._avt_parent[0]()._apply(fn)
-            return self
-        self._flat_store().apply(fn)
-        self._avt_engine = None
-        return self
-
     def _engine_and_params(self):
         from .engine import TrunkEngine
 
-        if self._avt_parent is not None:
-            parent, prefix = self._avt_parent[0](), self._avt_parent[1]
-            if parent is None:
-                raise RuntimeError("avt: the AVENet owning this trunk no longer exists")
-            if getattr(parent, prefix.rstrip("."), None) is not self:
-                raise RuntimeError("avt: this trunk is no longer its parent's (a copied trunk; copy the whole model)")
-            flat = parent._flat
-        else:
-            parent, prefix, flat = self, "", self._flat_store()
+        parent, prefix, flat = self._resolve()
         if self._avt_engine is None or self._avt_engine.flat is not flat:
             self._avt_engine = TrunkEngine(flat, prefix, self.modal)
-        named = dict(parent.named_parameters())
+        named = dict((parent or self).named_parameters())
         names = [n for n in flat.pnames if flat.trainable(n) and n.startswith(prefix)]
         return self._avt_engine, flat, names, [named[n] for n in names]
 
@@ -162,7 +132,7 @@ class ResNet(nn.Module):
     def _folded(self) -> bool:
         """The folded inference forward for this trunk called on its own: a FullModel's audio trunk follows its
         parent's ``enable_folded_inference()``; an AVENet's trunks and a standalone trunk keep the unfolded call."""
-        parent = self._avt_parent[0]() if self._avt_parent is not None else None
+        parent = self._resolve()[0]
         return bool(getattr(parent, "_avt_trunks_follow_fold", False) and getattr(parent, "_avt_folded", False))
 
 

@@ -23,10 +23,10 @@ folded into its conv (tube.R3DEngine.forward_folded); inside a FullMo
 """
 from __future__ import annotations
 
-import weakref
-
 import torch
 from torch import nn
+
+from .engine import FlatStore, ParentLink
 
 
 def get_inplanes():
@@ -55,7 +55,7 @@ class BasicBlock(nn.Module):
         self.stride = stride
 
 
-class ResNet(nn.Module):
+class ResNet(ParentLink, nn.Module):
     """resnet3D.ResNet(BasicBlock, layers, ...) parameter/buffer holder (shortcut 'B' only)."""
 
     def __init__(self, block, layers, block_inplanes, n_input_channels=3, conv1_t_size=7, conv1_t_stride=1,
@@ -111,9 +111,7 @@ class ResNet(nn.Module):
         return self
 
     def _folded(self) -> bool:
-        if self._avt_parent is not None and self._avt_parent[0]() is not None:
-            return bool(getattr(self._avt_parent[0](), "_avt_folded", False))
-        return bool(getattr(self, "_avt_folded", False))
+        return bool(getattr(self._resolve()[0] or self, "_avt_folded", False))
 
     def _make_layer(self, block, planes, blocks, stride=1):
         downsample = None  # built before the block, as resnet3D.py:169-184 (RNG order)
@@ -126,19 +124,7 @@ class ResNet(nn.Module):
             layers.append(block(self.in_planes, planes))
         return nn.Sequential(*layers)
 
-    def _adopt(self, parent, prefix: str):
-        self._avt_parent = (weakref.ref(parent), prefix)
-        self._own_flat = None
-        self._avt_engine = None
-
-    def __getstate__(self):
-        state = self.__dict__.copy()
-        state["_avt_engine"] = None
-        return state
-
     def _flat_store(self):
-        from .engine import FlatStore
-
         if self._own_flat is None:
             # nothing of the video trunk is trained unless enable_backward() was called (then: every parameter)
             self._own_flat = FlatStore(self, (lambda n: True) if self._avt_backward else (lambda n: False))
@@ -160,20 +146,10 @@ class ResNet(nn.Module):
         if not self._avt_backward:
             self._avt_backward = True
             if self._own_flat is not None:  # rebuild from the current parameter values (and device)
-                from .engine import FlatStore
-
                 self._own_flat = FlatStore(self, lambda n: True)
             self._avt_engine = None
         self._avt_input_grad = self._avt_input_grad or bool(input_grad)
         self._avt_eval_grad = self._avt_eval_grad or bool(eval_grad)
-        return self
-
-    def _apply(self, fn, recurse=True):
-        if self._avt_parent is not None and self._avt_parent[0]() is not None:
-            self._avt_parent[0]()._apply(fn)
-            return self
-        self._flat_store().apply(fn)
-        self._avt_engine = None
         return self
 
     def forward(self, x):
@@ -201,13 +177,7 @@ class ResNet(nn.Module):
             named = dict(self.named_parameters())
             names = [n for n in flat.pnames if named[n].requires_grad]
             return _R3DFunction.apply(self._avt_engine, names, self.training, x, *[named[n] for n in names])
-        if self._avt_parent is not None:
-            parent, prefix = self._avt_parent[0](), self._avt_parent[1]
-            if parent is None or getattr(parent, prefix.rstrip("."), None) is not self:
-                raise RuntimeError("avt: this R3D trunk is no longer its parent's (a copied trunk; copy the whole model)")
-            flat = parent._flat
-        else:
-            prefix, flat = "", self._flat_store()
+        _, prefix, flat = self._resolve()
         if self._avt_engine is None or self._avt_engine.flat is not flat:
             self._avt_engine = R3DEngine(flat, prefix, max_pool=not self.no_max_pool)
         if not self.training and self._folded():

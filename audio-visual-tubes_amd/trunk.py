@@ -17,7 +17,8 @@ import torch
 
 from ._lib import BnBwdTarget, DgradBnEpi, SlabReduceDesc, call, query
 
-STAGES = [(64, 1), (128, 2), (256, 2), (512, 1)]
+STAGES = [(64, 1), (128, 2), (256, 2), (512, 1)]  # (planes, stride of the stage's first block)
+DEPTHS = (2, 2, 2, 2)  # BasicBlocks per stage: ResNet-18, the 2-D trunks' and the R3D trunk's (tube.R3D_STAGES)
 # 1: BN-backward reductions fused into the dgrad epilogues (avt_conv2d_dgrad_bn); default 0: the separate
 # reduce/apply passes of avt_bn_bwd (measured 1 % faster: DESIGN §6f)
 FUSE_BN_BWD = os.environ.get("AVT_FUSE_BN_BWD", "0") == "1"
@@ -225,7 +226,130 @@ def _bn_finalize(c_out, acc, rows, bn: BNSpec, store: Store, training: bool, mom
     return stats
 
 
-class Trunk:
+def build_blocks(prefix: str, stages, depths, make_conv) -> List[Dict]:
+    """The BasicBlocks of layer1.. as dicts (conv1, bn1, conv2, bn2, down, bnd; the last two None without a
+    downsample), in forward order.  make_conv(name, cin, cout, k, stride) is all that differs between the trunks: the
+    spec of a k x k (x k) conv with padding k // 2 -- a ConvSpec, or a tube.Conv3dSpec."""
+    blocks, inplanes = [], stages[0][0]  # (the stem's output channels)
+    for li, ((planes, stride), depth) in enumerate(zip(stages, depths), start=1):
+        for bi in range(depth):
+            s = stride if bi == 0 else 1
+            p = f"{prefix}layer{li}.{bi}."
+            cin = inplanes if bi == 0 else planes
+            blk = {
+                "conv1": make_conv(p + "conv1.weight", cin, planes, 3, s),
+                "bn1": BNSpec(p + "bn1", planes),
+                "conv2": make_conv(p + "conv2.weight", planes, planes, 3, 1),
+                "bn2": BNSpec(p + "bn2", planes),
+                "down": None,
+                "bnd": None,
+            }
+            if bi == 0 and (s != 1 or inplanes != planes):
+                blk["down"] = make_conv(p + "downsample.0.weight", inplanes, planes, 1, s)
+                blk["bnd"] = BNSpec(p + "downsample.1", planes)
+            blocks.append(blk)
+        inplanes = planes
+    return blocks
+
+
+class BlockGraph:
+    """What Trunk and tube.R3DTrunk share: the graph (stem, bn1, blocks), its walks, the two block indices the
+    engines cut it at, and the BatchNorm-backward launches (the same kernels over [rows, C] in 2-D and 3-D)."""
+
+    # backward boundary: once layer3 and layer4 are done (~94 % of a ResNet-18's parameters) their
+    # gradients can start their all-reduce while layer2..stem run (train.py bucketing)
+    HI_BLOCK = sum(DEPTHS[:2])  # index of layer3.0 in self.blocks
+    LAYER4_BLOCK = sum(DEPTHS[:3])  # index of layer4.0: its input is what a forward hook on .layer4 sees
+
+    def conv_bn_pairs(self) -> List[tuple]:
+        """Every (conv, its BatchNorm) in state_dict order: the stem, then per block conv1, conv2, downsample."""
+        out = [(self.stem, self.bn1)]
+        for b in self.blocks:
+            out += [(b["conv1"], b["bn1"]), (b["conv2"], b["bn2"])] + ([(b["down"], b["bnd"])] if b["down"] else [])
+        return out
+
+    def convs(self) -> List:
+        return [c for c, _ in self.conv_bn_pairs()]
+
+    def bns(self) -> List[BNSpec]:
+        return [b for _, b in self.conv_bn_pairs()]
+
+    # ------------------------------------------------------------------ BatchNorm backward
+    def _bn_bwd(self, g, y, xc, stats, bn: BNSpec, store: Store, gmask_out=None):
+        """avt_bn_bwd: g' = g * [y > 0] (y None: no mask; gmask_out receives g') -> the gradient of the pre-BN
+        activation xc; d(gamma, beta)."""
+        rows = xc.numel() // bn.c
+        gc = torch.empty_like(xc)
+        ws = store.stat_acc(bn, "bwd", rows)
+        call("avt_bn_bwd", P(g), P(y), P(xc), P(stats[2]), P(stats[3]), P(store.param(bn.prefix + ".weight")),
+             P(store.grad(bn.prefix + ".weight")), P(store.grad(bn.prefix + ".bias")), P(gc), P(gmask_out), P(ws),
+             rows, bn.c, stream_ptr())
+        return gc
+
+    def _bn_relu_bwd(self, g, xc, stats, bn: BNSpec, store: Store):
+        """bn -> relu backward with the mask recomputed from (xc, scale, shift) as the forward's avt_bn_apply made
+        it (BasicBlock.bn1, the R3D stem)."""
+        rows = xc.numel() // bn.c
+        gc = torch.empty_like(xc)
+        ws = store.stat_acc(bn, "bwd", rows)
+        call("avt_bn_relu_bwd", P(g), P(xc), P(stats[0]), P(stats[1]), P(stats[2]), P(stats[3]),
+             P(store.param(bn.prefix + ".weight")), P(store.grad(bn.prefix + ".weight")),
+             P(store.grad(bn.prefix + ".bias")), P(gc), P(ws), rows, bn.c, stream_ptr())
+        return gc
+
+    def _bn_bwd_premasked(self, gm, xc, stats, bn: BNSpec, store: Store):
+        """BN backward of a pre-masked g' whose reductions a dgrad epilogue already accumulated."""
+        gc = torch.empty_like(xc)
+        call("avt_bn_bwd_premasked", P(gm), P(xc), P(stats[2]), P(stats[3]), P(store.param(bn.prefix + ".weight")),
+             P(store.grad(bn.prefix + ".weight")), P(store.grad(bn.prefix + ".bias")), P(gc),
+             P(store.stat_acc(bn, "bwd", xc.numel() // bn.c)), xc.numel() // bn.c, bn.c, stream_ptr())
+        return gc
+
+    def _target(self, xc, stats, bn: BNSpec, store: Store, pgrad: bool = True) -> BnBwdTarget:
+        """One BN of a launch that takes avt_bn_bwd_target structs; its output gc is t.keep.
+        pgrad=False (eval backward with frozen parameters): no dgamma / dbeta, no workspace."""
+        t = BnBwdTarget()
+        gc = torch.empty_like(xc)
+        t.xc, t.mean, t.invstd = xc.data_ptr(), stats[2].data_ptr(), stats[3].data_ptr()
+        t.gamma = store.param(bn.prefix + ".weight").data_ptr()
+        if pgrad:
+            dg, db = store.grad(bn.prefix + ".weight"), store.grad(bn.prefix + ".bias")
+            t.dgamma = dg.data_ptr() if dg is not None else None
+            t.dbeta = db.data_ptr() if db is not None else None
+            t.workspace = store.stat_acc(bn, "bwd", xc.numel() // bn.c).data_ptr()
+        t.gc = gc.data_ptr()
+        t.keep = gc  # the output tensor (ctypes.Structure keeps no reference)
+        return t
+
+    def _bn_bwd_mask(self, g, mask, xc, stats, bn: BNSpec, store: Store, xc2=None, stats2=None, bn2=None,
+                     entry: str = "avt_bn_bwd_mask", pgrad: bool = True):
+        """Block-output BN backward(s) from the ReLU mask bits: bn2 alone, or bn2 + downsample.1 in one
+        pass.  Returns the gradient(s) of the pre-BN activation(s)."""
+        t1 = self._target(xc, stats, bn, store, pgrad)
+        t2 = self._target(xc2, stats2, bn2, store, pgrad) if bn2 is not None else None
+        call(entry, P(g), P(mask), ctypes.byref(t1), ctypes.byref(t2) if t2 is not None else None,
+             xc.numel() // bn.c, bn.c, stream_ptr())
+        return t1.keep, (t2.keep if t2 is not None else None)
+
+    def _bn_eval_bwd_mask(self, g, mask, xc, stats, bn: BNSpec, store: Store, pgrad: bool, xc2=None, stats2=None,
+                          bn2=None):
+        """_bn_bwd_mask under running statistics (avt_bn_eval_bwd_mask): one pass, gc = gamma*invstd*g*bit."""
+        return self._bn_bwd_mask(g, mask, xc, stats, bn, store, xc2, stats2, bn2, "avt_bn_eval_bwd_mask", pgrad)
+
+    def _bn_eval_bwd(self, g, xc, stats, bn: BNSpec, store: Store, pgrad: bool = True, y=None, mask_stats=None,
+                     gmask_out=None, second=None):
+        """avt_bn_eval_bwd: the running-statistics rule gc = gamma * invstd * g' (one pass).  Mask from y, from
+        mask_stats = (scale, shift) on xc (_bn_relu_bwd's rule), or none; gmask_out receives g'; second = (xc2, stats2,
+        bn2): a BN sharing g' -> (gc, gc2)."""
+        t1 = self._target(xc, stats, bn, store, pgrad)
+        t2 = self._target(*second, store, pgrad) if second is not None else None
+        ms = (None, None) if mask_stats is None else (mask_stats[0], mask_stats[1])
+        call("avt_bn_eval_bwd", P(g), P(y), P(ms[0]), P(ms[1]), ctypes.byref(t1),
+             ctypes.byref(t2) if t2 is not None else None, P(gmask_out), xc.numel() // bn.c, bn.c, stream_ptr())
+        return t1.keep if second is None else (t1.keep, t2.keep)
+
+
+class Trunk(BlockGraph):
     """One ResNet-18 (base_models.resnet18(modal=...)) on libavt."""
 
     def __init__(self, prefix: str, modal: str):
@@ -237,38 +361,8 @@ class Trunk:
         else:
             self.stem = ConvSpec(prefix + "conv1.weight", 3, 64, 7, 2, 3, 4)
         self.bn1 = BNSpec(prefix + "bn1", 64)
-        self.blocks = []
-        inplanes = 64
-        for li, (planes, stride) in enumerate(STAGES, start=1):
-            for bi in range(2):
-                s = stride if bi == 0 else 1
-                p = f"{prefix}layer{li}.{bi}."
-                cin = inplanes if bi == 0 else planes
-                blk = {
-                    "conv1": ConvSpec(p + "conv1.weight", cin, planes, 3, s, 1, cin),
-                    "bn1": BNSpec(p + "bn1", planes),
-                    "conv2": ConvSpec(p + "conv2.weight", planes, planes, 3, 1, 1, planes),
-                    "bn2": BNSpec(p + "bn2", planes),
-                    "down": None,
-                    "bnd": None,
-                }
-                if bi == 0 and (s != 1 or inplanes != planes):
-                    blk["down"] = ConvSpec(p + "downsample.0.weight", inplanes, planes, 1, s, 0, inplanes)
-                    blk["bnd"] = BNSpec(p + "downsample.1", planes)
-                self.blocks.append(blk)
-            inplanes = planes
-
-    def convs(self) -> List[ConvSpec]:
-        out = [self.stem]
-        for b in self.blocks:
-            out += [b["conv1"], b["conv2"]] + ([b["down"]] if b["down"] is not None else [])
-        return out
-
-    def bns(self) -> List[BNSpec]:
-        out = [self.bn1]
-        for b in self.blocks:
-            out += [b["bn1"], b["bn2"]] + ([b["bnd"]] if b["bnd"] is not None else [])
-        return out
+        self.blocks = build_blocks(prefix, STAGES, DEPTHS,
+                                   lambda name, cin, cout, k, s: ConvSpec(name, cin, cout, k, s, k // 2, cin))
 
     # ------------------------------------------------------------------ forward
     def _conv_bn(self, x, N, H, W, spec: ConvSpec, bn: BNSpec, store: Store, training: bool):
@@ -319,7 +413,7 @@ class Trunk:
         yield
         cur, Hc, Wc = p0, H2, W2
         for bi, blk in enumerate(self.blocks):
-            if io is not None and bi == 6:
+            if io is not None and bi == self.LAYER4_BLOCK:
                 io["layer4_in"] = cur
             t = {"x": cur, "H": Hc, "W": Wc}
             c1, s1, Ho, Wo = self._conv_bn(cur, N, Hc, Wc, blk["conv1"], blk["bn1"], store, training)
@@ -399,7 +493,7 @@ class Trunk:
         yield
         cur, Hc, Wc = p0, H2, W2
         for bi, blk in enumerate(self.blocks):
-            if io is not None and bi == 6:
+            if io is not None and bi == self.LAYER4_BLOCK:
                 io["layer4_in"] = cur
             h1, Ho, Wo = self._conv_bias(cur, N, Hc, Wc, blk["conv1"], store, True)
             yield
@@ -413,65 +507,6 @@ class Trunk:
         return cur
 
     # ------------------------------------------------------------------ backward
-    def _bn_bwd(self, g, y, xc, stats, bn: BNSpec, store: Store, gmask_out=None):
-        rows = xc.numel() // bn.c
-        gc = torch.empty_like(xc)
-        ws = store.stat_acc(bn, "bwd", rows)
-        call("avt_bn_bwd", P(g), P(y), P(xc), P(stats[2]), P(stats[3]), P(store.param(bn.prefix + ".weight")),
-             P(store.grad(bn.prefix + ".weight")), P(store.grad(bn.prefix + ".bias")), P(gc), P(gmask_out), P(ws),
-             rows, bn.c, stream_ptr())
-        return gc
-
-    def _target(self, xc, stats, bn: BNSpec, store: Store, pgrad: bool = True) -> BnBwdTarget:
-        """pgrad=False (eval backward with frozen parameters): no dgamma / dbeta, no workspace."""
-        t = BnBwdTarget()
-        gc = torch.empty_like(xc)
-        t.xc, t.mean, t.invstd = xc.data_ptr(), stats[2].data_ptr(), stats[3].data_ptr()
-        t.gamma = store.param(bn.prefix + ".weight").data_ptr()
-        if pgrad:
-            dg, db = store.grad(bn.prefix + ".weight"), store.grad(bn.prefix + ".bias")
-            t.dgamma = dg.data_ptr() if dg is not None else None
-            t.dbeta = db.data_ptr() if db is not None else None
-            t.workspace = store.stat_acc(bn, "bwd", xc.numel() // bn.c).data_ptr()
-        t.gc = gc.data_ptr()
-        t.keep = gc  # the output tensor (ctypes.Structure keeps no reference)
-        return t
-
-    def _bn_eval_bwd_mask(self, g, mask, xc, stats, bn: BNSpec, store: Store, pgrad: bool, xc2=None, stats2=None,
-                          bn2=None):
-        """_bn_bwd_mask under running statistics (avt_bn_eval_bwd_mask): one pass, gc = gamma*invstd*g*bit."""
-        t1 = self._target(xc, stats, bn, store, pgrad)
-        t2 = self._target(xc2, stats2, bn2, store, pgrad) if bn2 is not None else None
-        call("avt_bn_eval_bwd_mask", P(g), P(mask), ctypes.byref(t1), ctypes.byref(t2) if t2 is not None else None,
-             xc.numel() // bn.c, bn.c, stream_ptr())
-        return t1.keep, (t2.keep if t2 is not None else None)
-
-    def _bn_eval_relu_bwd(self, g, xc, stats, bn: BNSpec, store: Store, pgrad: bool):
-        """_bn_relu_bwd under running statistics (avt_bn_eval_bwd, mask recomputed from (xc, scale, shift))."""
-        t1 = self._target(xc, stats, bn, store, pgrad)
-        call("avt_bn_eval_bwd", P(g), None, P(stats[0]), P(stats[1]), ctypes.byref(t1), None, None,
-             xc.numel() // bn.c, bn.c, stream_ptr())
-        return t1.keep
-
-    def _bn_bwd_mask(self, g, mask, xc, stats, bn: BNSpec, store: Store, xc2=None, stats2=None, bn2=None):
-        """Block-output BN backward(s) from the ReLU mask bits: bn2 alone, or bn2 + downsample.1 in one
-        pass (avt_bn_bwd_mask).  Returns the gradient(s) of the pre-BN activation(s)."""
-        t1 = self._target(xc, stats, bn, store)
-        t2 = self._target(xc2, stats2, bn2, store) if bn2 is not None else None
-        call("avt_bn_bwd_mask", P(g), P(mask), ctypes.byref(t1), ctypes.byref(t2) if t2 is not None else None,
-             xc.numel() // bn.c, bn.c, stream_ptr())
-        return t1.keep, (t2.keep if t2 is not None else None)
-
-    def _bn_relu_bwd(self, g, xc, stats, bn: BNSpec, store: Store):
-        """bn -> relu backward with the mask recomputed from (xc, scale, shift) (BasicBlock.bn1)."""
-        rows = xc.numel() // bn.c
-        gc = torch.empty_like(xc)
-        ws = store.stat_acc(bn, "bwd", rows)
-        call("avt_bn_relu_bwd", P(g), P(xc), P(stats[0]), P(stats[1]), P(stats[2]), P(stats[3]),
-             P(store.param(bn.prefix + ".weight")), P(store.grad(bn.prefix + ".weight")),
-             P(store.grad(bn.prefix + ".bias")), P(gc), P(ws), rows, bn.c, stream_ptr())
-        return gc
-
     def _wgrad(self, x, gy, N, H, W, spec: ConvSpec, store: Store):
         dw = store.grad(spec.name)
         wsb = int(query("avt_conv2d_wgrad_workspace", N, H, W, spec.cp, spec.cin, spec.cout, spec.k, spec.k,
@@ -528,24 +563,12 @@ class Trunk:
                          2.0 * (gy.numel() + wt.numel() + gx.numel() * (2 if add is not None else 1)))
         return gx
 
-    # backward boundary: once layer3 and layer4 are done (~94 % of a ResNet-18's parameters) their
-    # gradients can start their all-reduce while layer2..stem run (train.py bucketing)
-    HI_BLOCK = 4  # index of layer3.0 in self.blocks
-
     def backward(self, tape: Dict, g_out: torch.Tensor, store: Store, on_boundary=None):
         g, pm = self.backward_blocks(tape, g_out, store, self.HI_BLOCK, len(self.blocks))
         if on_boundary is not None:
             on_boundary(self.prefix + "hi")
         g, _ = self.backward_blocks(tape, g, store, 0, self.HI_BLOCK, pm)
         self.backward_stem(tape, g, store)
-
-    def _bn_bwd_premasked(self, gm, xc, stats, bn: BNSpec, store: Store):
-        """BN backward of a pre-masked g' whose reductions a dgrad epilogue already accumulated."""
-        gc = torch.empty_like(xc)
-        call("avt_bn_bwd_premasked", P(gm), P(xc), P(stats[2]), P(stats[3]), P(store.param(bn.prefix + ".weight")),
-             P(store.grad(bn.prefix + ".weight")), P(store.grad(bn.prefix + ".bias")), P(gc),
-             P(store.stat_acc(bn, "bwd", xc.numel() // bn.c)), xc.numel() // bn.c, bn.c, stream_ptr())
-        return gc
 
     def _epi(self, store: Store, bn: BNSpec, xc, stats, y=None, bn2: Optional[BNSpec] = None, xc2=None, stats2=None,
              skip00: bool = False, append: bool = False) -> DgradBnEpi:
@@ -614,7 +637,7 @@ class Trunk:
                 g_h1 = self._dgrad(g_c2, N, Ho, Wo, blk["conv2"], store)
                 yield
                 if ev:
-                    g_c1 = self._bn_eval_relu_bwd(g_h1, t["c1"], t["s1"], blk["bn1"], store, pgrad)
+                    g_c1 = self._bn_eval_bwd(g_h1, t["c1"], t["s1"], blk["bn1"], store, pgrad, mask_stats=t["s1"])
                 else:
                     g_c1 = self._bn_relu_bwd(g_h1, t["c1"], t["s1"], blk["bn1"], store)
             yield

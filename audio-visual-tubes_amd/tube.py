@@ -33,15 +33,13 @@ gradient for the shared forward), and cuts the audio trunk's work by t.  Given t
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import Dict, List, Optional
+from typing import Dict, Optional
 
 import torch
 
-import ctypes
-
-from ._lib import BnBwdTarget, call, query
-from .engine import AVEngine, FlatStore, _EngineStore
-from .trunk import BNSpec, ConvProfiler, P, Trunk, _bn_finalize, conv_out, stream_ptr
+from ._lib import call, query
+from .engine import AVEngine, FlatStore, _EngineStore, desc_table
+from .trunk import DEPTHS, BlockGraph, BNSpec, ConvProfiler, P, Trunk, _bn_finalize, build_blocks, conv_out, stream_ptr
 
 R3D_STAGES = [(64, 1), (128, 2), (256, 2), (512, 2)]  # (planes, spatial stride) — resnet3D.py:136-150
 
@@ -82,7 +80,7 @@ class Conv3dSpec:
         return self.k * self.k * 32 if self.stem else self.kt * self.k * self.k * self.cin
 
 
-class R3DTrunk:
+class R3DTrunk(BlockGraph):
     """resnet3D ResNet(BasicBlock, [2,2,2,2]) up to layer4, forward and (from a tape) backward; no_max_pool=True
     (FullModel, model.py:20) unless max_pool (the stem's MaxPool3d(3, 2, 1), resnet3D.py:129, 200-201)."""
 
@@ -91,38 +89,8 @@ class R3DTrunk:
         self.max_pool = max_pool
         self.stem = Conv3dSpec(prefix + "conv1.weight", 3, 64, 7, 7, 2, 3, 3, stem=True)
         self.bn1 = BNSpec(prefix + "bn1", 64)
-        self.blocks = []
-        inplanes = 64
-        for li, (planes, stride) in enumerate(R3D_STAGES, start=1):
-            for bi in range(2):
-                s = stride if bi == 0 else 1
-                p = f"{prefix}layer{li}.{bi}."
-                cin = inplanes if bi == 0 else planes
-                blk = {
-                    "conv1": Conv3dSpec(p + "conv1.weight", cin, planes, 3, 3, s, 1, 1),
-                    "bn1": BNSpec(p + "bn1", planes),
-                    "conv2": Conv3dSpec(p + "conv2.weight", planes, planes, 3, 3, 1, 1, 1),
-                    "bn2": BNSpec(p + "bn2", planes),
-                    "down": None,
-                    "bnd": None,
-                }
-                if bi == 0 and (s != 1 or inplanes != planes):
-                    blk["down"] = Conv3dSpec(p + "downsample.0.weight", inplanes, planes, 1, 1, s, 0, 0)
-                    blk["bnd"] = BNSpec(p + "downsample.1", planes)
-                self.blocks.append(blk)
-            inplanes = planes
-
-    def convs(self) -> List[Conv3dSpec]:
-        out = [self.stem]
-        for b in self.blocks:
-            out += [b["conv1"], b["conv2"]] + ([b["down"]] if b["down"] is not None else [])
-        return out
-
-    def bns(self) -> List[BNSpec]:
-        out = [self.bn1]
-        for b in self.blocks:
-            out += [b["bn1"], b["bn2"]] + ([b["bnd"]] if b["bnd"] is not None else [])
-        return out
+        self.blocks = build_blocks(prefix, R3D_STAGES, DEPTHS,
+                                   lambda name, cin, cout, k, s: Conv3dSpec(name, cin, cout, k, k, s, k // 2, k // 2))
 
     def _conv(self, x, b, T, H, W, spec: Conv3dSpec, bn: BNSpec, store, training):
         """Conv3d (+ BN statistics) -> (y [b*T, H', W', K] bf16, stats [4, K], H', W')."""
@@ -248,53 +216,11 @@ class R3DTrunk:
         return h
 
     # ------------------------------------------------------------------ backward
-    @staticmethod
-    def _eval_target(xc, stats, bn: BNSpec, store):
-        """(avt_bn_bwd_target of one eval-mode BN, its gc): stats = the running-statistics (scale, shift, mean, invstd)."""
-        t, gc = BnBwdTarget(), torch.empty_like(xc)
-        t.xc, t.mean, t.invstd, t.gc = xc.data_ptr(), stats[2].data_ptr(), stats[3].data_ptr(), gc.data_ptr()
-        t.gamma = store.param(bn.prefix + ".weight").data_ptr()
-        t.dgamma, t.dbeta = store.grad(bn.prefix + ".weight").data_ptr(), store.grad(bn.prefix + ".bias").data_ptr()
-        t.workspace = store.stat_acc(bn, "bwd", xc.numel() // bn.c).data_ptr()
-        return t, gc
-
-    @classmethod
-    def _bn_eval_bwd(cls, g, y, mask_stats, xc, stats, bn: BNSpec, store, gmask_out=None, second=None):
-        """avt_bn_eval_bwd: the running-statistics rule gc = gamma * invstd * g' (one pass).  Mask from y, from
-        mask_stats = (scale, shift) on xc, or none; second = (xc2, stats2, bn2): a BN sharing g' -> (gc, gc2)."""
-        t1, gc = cls._eval_target(xc, stats, bn, store)
-        t2 = gc2 = None
-        if second is not None:
-            t2, gc2 = cls._eval_target(second[0], second[1], second[2], store)
-        ms = (None, None) if mask_stats is None else (mask_stats[0], mask_stats[1])
-        call("avt_bn_eval_bwd", P(g), P(y), P(ms[0]), P(ms[1]), ctypes.byref(t1),
-             ctypes.byref(t2) if t2 is not None else None, P(gmask_out), xc.numel() // bn.c, bn.c, stream_ptr())
-        return gc if second is None else (gc, gc2)
-
-    @classmethod
-    def _bn_bwd(cls, g, y, xc, stats, bn: BNSpec, store, gmask_out=None, training=True):
-        """avt_bn_bwd: g' = g * [y > 0] (y None: no mask) -> the gradient of the pre-BN activation xc; d(gamma, beta).
-        training=False: the eval-mode rule (avt_bn_eval_bwd)."""
-        if not training:
-            return cls._bn_eval_bwd(g, y, None, xc, stats, bn, store, gmask_out=gmask_out)
-        rows = xc.numel() // bn.c
-        gc = torch.empty_like(xc)
-        call("avt_bn_bwd", P(g), P(y), P(xc), P(stats[2]), P(stats[3]), P(store.param(bn.prefix + ".weight")),
-             P(store.grad(bn.prefix + ".weight")), P(store.grad(bn.prefix + ".bias")), P(gc), P(gmask_out),
-             P(store.stat_acc(bn, "bwd", rows)), rows, bn.c, stream_ptr())
-        return gc
-
-    @classmethod
-    def _bn_relu_bwd(cls, g, xc, stats, bn: BNSpec, store, training=True):
-        """bn -> relu backward, the mask recomputed from (xc, scale, shift) as the forward's avt_bn_apply made it."""
-        if not training:
-            return cls._bn_eval_bwd(g, None, stats, xc, stats, bn, store)
-        rows = xc.numel() // bn.c
-        gc = torch.empty_like(xc)
-        call("avt_bn_relu_bwd", P(g), P(xc), P(stats[0]), P(stats[1]), P(stats[2]), P(stats[3]),
-             P(store.param(bn.prefix + ".weight")), P(store.grad(bn.prefix + ".weight")),
-             P(store.grad(bn.prefix + ".bias")), P(gc), P(store.stat_acc(bn, "bwd", rows)), rows, bn.c, stream_ptr())
-        return gc
+    def _bn_relu(self, g, xc, stats, bn: BNSpec, store, training: bool):
+        """bn -> relu backward by the train rule, or (training=False) the running-statistics one."""
+        if training:
+            return self._bn_relu_bwd(g, xc, stats, bn, store)
+        return self._bn_eval_bwd(g, xc, stats, bn, store, mask_stats=stats)
 
     @staticmethod
     def _wgrad(x, gy, b, T, H, W, spec: Conv3dSpec, store):
@@ -328,8 +254,6 @@ class R3DTrunk:
                          2.0 * (gy.numel() + wt.numel() + gx.numel()))
         return gx
 
-    HI_BLOCK = 4  # index of layer3.0 in self.blocks (the gradient buckets' boundary, as Trunk.HI_BLOCK)
-
     def backward(self, tape, g: torch.Tensor, store, training: bool = True, gvideo=None, on_boundary=None) -> None:
         """g bf16 [b*T, h, w, 512] = d(loss)/d(layer4 map) -> the trunk's parameter gradients, accumulated into
         store.grad(name) (zeroed by the caller).  Blocks in reverse, unfused (autograd through BasicBlock.forward,
@@ -352,17 +276,19 @@ class R3DTrunk:
         for blk, tb in zip(reversed(self.blocks[lo:hi]), reversed(tape["blocks"][lo:hi])):
             T, H, W, Ho, Wo = tb["dims"]
             gm = gcd = None
-            if training or blk["down"] is None:
-                gm = torch.empty_like(g)  # g * [out > 0]: shared by bn2, downsample.1 and the identity residual
-                gc2 = self._bn_bwd(g, tb["out"], tb["c2"], tb["s2"], blk["bn2"], store, gmask_out=gm,
-                                   training=training)
-            else:
-                gc2, gcd = self._bn_eval_bwd(g, tb["out"], None, tb["c2"], tb["s2"], blk["bn2"], store,
+            if not training and blk["down"] is not None:  # the eval rule takes bn2 and downsample.1 in one pass
+                gc2, gcd = self._bn_eval_bwd(g, tb["c2"], tb["s2"], blk["bn2"], store, y=tb["out"],
                                              second=(tb["cd"], tb["sd"], blk["bnd"]))
+            else:
+                gm = torch.empty_like(g)  # g * [out > 0]: shared by bn2, downsample.1 and the identity residual
+                if training:
+                    gc2 = self._bn_bwd(g, tb["out"], tb["c2"], tb["s2"], blk["bn2"], store, gmask_out=gm)
+                else:
+                    gc2 = self._bn_eval_bwd(g, tb["c2"], tb["s2"], blk["bn2"], store, y=tb["out"], gmask_out=gm)
             self._wgrad(tb["h1"], gc2, b, T, Ho, Wo, blk["conv2"], store)
             gh1 = self._dgrad(gc2, b, T, Ho, Wo, blk["conv2"], store)
             del gc2
-            gc1 = self._bn_relu_bwd(gh1, tb["c1"], tb["s1"], blk["bn1"], store, training=training)
+            gc1 = self._bn_relu(gh1, tb["c1"], tb["s1"], blk["bn1"], store, training)
             del gh1
             self._wgrad(tb["x"], gc1, b, T, H, W, blk["conv1"], store)
             if blk["down"] is not None:
@@ -385,7 +311,7 @@ class R3DTrunk:
             gp = torch.empty_like(tape["h0"])
             call("avt_maxpool3d_bwd", P(g), P(tape["h0"]), None, P(gp), b, T, H, W, 64, stream_ptr())
             g = gp
-        gc0 = self._bn_relu_bwd(g, tape["c0"], tape["s0"], self.bn1, store, training=training)
+        gc0 = self._bn_relu(g, tape["c0"], tape["s0"], self.bn1, store, training)
         # the stem's weight gradient in its folded layout: a 2-D wgrad over the 32-channel im2col input, unfolded
         st, x = self.stem, tape["x"]
         Ti, Hi, Wi = tape["dims"]
@@ -417,8 +343,7 @@ def _alloc_packs3d(engine, dev):
             descs.append(struct.pack("<QQiiii", engine.flat.raw(spec.name).data_ptr(), wp.data_ptr(), spec.cout,
                                      spec.cin, t, 0))
             max_k, max_row = max(max_k, spec.cout), max(max_row, spec.cin * t)
-    assert descs and len(descs[0]) == int(query("avt_pack3d_desc_bytes"))
-    engine._pack3d_table = torch.frombuffer(bytearray(b"".join(descs)), dtype=torch.uint8).to(dev)
+    engine._pack3d_table = desc_table(descs, "avt_pack3d_desc_bytes", dev)
     engine._pack3d_n, engine._pack3d_max = len(descs), (max_k, max_row)
     engine._pack3d_t_table = None
     if getattr(engine, "with_backward", False):  # the dgrad operands [cin][taps * cout] of the same convs
@@ -432,13 +357,13 @@ def _alloc_packs3d(engine, dev):
             descs.append(struct.pack("<QQiiii", engine.flat.raw(spec.name).data_ptr(), wt.data_ptr(), spec.cout,
                                      spec.cin, t, 0))
             max_blocks = max(max_blocks, spec.cin * (spec.cout // 64))
-        engine._pack3d_t_table = torch.frombuffer(bytearray(b"".join(descs)), dtype=torch.uint8).to(dev)
+        engine._pack3d_t_table = desc_table(descs, None, dev)  # (the record layout checked above)
         engine._pack3d_t_n, engine._pack3d_t_blocks = len(descs), max_blocks
 
 
 def _pack3d(engine, stem_dgrad: bool = False):
     """vidnet weights (fp32 OIDHW, never updated by the optimizer) -> bf16 fwd operands, repacked every step so a
-    load_state_dict is always picked up: the folded stem (its own layout) and one launch for the other 19 convs.
+    load_state_dict is always picked up: the folded stem (its own layout) and one launch for all the other convs.
     stem_dgrad (a step whose video requires grad): the stem's dgrad operand too (avt_video_stem_dgrad's MFMA form)."""
     stem = engine.vid.stem
     call("avt_pack_conv3d_weight", P(engine.flat.raw(stem.name)), P(engine.packs3d[stem.name]), stem.cout, stem.cin,
@@ -458,20 +383,15 @@ def _pack3d(engine, stem_dgrad: bool = False):
 
 def _alloc_folds3d(engine):
     """The folded operands of the video trunk (first folded forward), kept next to packs3d: per conv the bf16 image
-    of w * bn_scale (the stem in its 32-channel layout) and the fp32 bias, and the device table of all 21 records
-    for avt_fold_conv3d_bn_batched."""
+    of w * bn_scale (the stem in its 32-channel layout) and the fp32 bias, and the device table of one record per
+    (conv, BN) pair for avt_fold_conv3d_bn_batched."""
     import struct
 
     flat, vid = engine.flat, engine.vid
     dev = flat.flat.device
-    pairs = [(vid.stem, vid.bn1)]
-    for blk in vid.blocks:
-        pairs += [(blk["conv1"], blk["bn1"]), (blk["conv2"], blk["bn2"])]
-        if blk["down"] is not None:
-            pairs.append((blk["down"], blk["bnd"]))
     engine.folds3d = {}
     descs, max_k, max_row = [], 1, 1
-    for spec, bn in pairs:
+    for spec, bn in vid.conv_bn_pairs():
         wf = torch.empty(spec.cout, spec.kg, device=dev, dtype=torch.bfloat16)
         bias = torch.empty(spec.cout, device=dev, dtype=torch.float32)
         engine.folds3d[spec.name] = (wf, bias)
@@ -480,8 +400,7 @@ def _alloc_folds3d(engine):
         descs.append(struct.pack("<QQQQQQQiiiiiifi", *[t.data_ptr() for t in ptrs], spec.cout, spec.cin, spec.kt,
                                  spec.k, spec.k, int(spec.stem), AVEngine.BN_EPS, 0))
         max_k, max_row = max(max_k, spec.cout), max(max_row, spec.cin * spec.kt * spec.k * spec.k)
-    assert len(descs[0]) == int(query("avt_fold3d_desc_bytes"))
-    engine._fold3d_table = torch.frombuffer(bytearray(b"".join(descs)), dtype=torch.uint8).to(dev)
+    engine._fold3d_table = desc_table(descs, "avt_fold3d_desc_bytes", dev)
     engine._fold3d_n, engine._fold3d_max = len(descs), (max_k, max_row)
 
 
@@ -690,8 +609,7 @@ class TubeEngine(AVEngine):
         B, C, rep, Ba = tape["B"], tape["C"], tape["rep"], tape["Ba"]
         gv, gan = self.head_backward(tape, dlogits, dA=dA)
         a, aud, vid, ta, tv = tape["a"], self.aud, self.vid, tape["aud"], tape["vid"]
-        hi = aud.HI_BLOCK
-        assert hi == vid.HI_BLOCK
+        hi = aud.HI_BLOCK  # (BlockGraph's: the same index in both trunks)
 
         def audio_hi():
             if rep > 1:
