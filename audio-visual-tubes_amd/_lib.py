@@ -16,7 +16,7 @@ CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_PATH = os.path.join(PKG_DIR, "libavt.so")
 # A/B measurement only: load another in-tree build of the same ABI (e.g. libavt_base.so)
 LOAD_PATH = os.environ.get("AVT_LIB_PATH", LIB_PATH)
-SOURCES = ["conv_gemm.hip", "bn.hip", "pool.hip", "head.hip", "misc.hip", "tube.hip", "conv3d_bwd.hip", "eval.hip", "audio.hip", "frames.hip", "render.hip"]
+SOURCES = ["conv_gemm.hip", "bn.hip", "pool.hip", "head.hip", "misc.hip", "tube.hip", "conv3d_bwd.hip", "eval.hip", "audio.hip", "frames.hip", "render.hip", "cls.hip"]
 
 _P = ctypes.c_void_p
 _I = ctypes.c_int
@@ -172,6 +172,13 @@ SIGNATURES = {
     "avt_adam_step_dev": (_I, [_P, _P, _P, _P, _L, _F, _P, _P, _P, _P]),
     "avt_adam_prep_dev": (_I, [_P, _P, _P, _P]),
     "avt_adam_apply_dev": (_I, [_P, _P, _P, _P, _L, _F, _P, _P]),
+    "avt_sgd_step_dev": (_I, [_P, _P, _P, _L, _F, _P, _P, _P]),
+    "avt_cls_pool_ws_bytes": (_Z, [_I, _L, _I]),
+    "avt_cls_pool_fwd": (_I, [_P, _P, _I, _L, _I, _P, _Z, _P]),
+    "avt_cls_pool_bwd": (_I, [_P, _P, _I, _L, _I, _P]),
+    "avt_cls_fc_fwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
+    "avt_cls_fc_bwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
+    "avt_softmax_ce": (_I, [_P, _P, _I, _I, _F, _P, _P, _P, _P]),
     "avt_pack_conv_weights_part": (_I, [_P, _I, _L, _I, _P]),
     "avt_pack_conv_weight": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     "avt_pack_desc_bytes": (_Z, []),
@@ -281,7 +288,7 @@ def lib() -> ctypes.CDLL:
 # inference path (engine.AVEngine.fold_state) compares; a replayed HIP graph that holds such a launch must call
 # note_param_write() itself (train.py does).
 PARAM_WRITERS = frozenset({"avt_adam_step", "avt_adam_step_dev", "avt_adam_apply_dev", "avt_bn_finalize",
-                           "avt_bn_finalize_rep"})
+                           "avt_bn_finalize_rep", "avt_sgd_step_dev"})
 _param_write_gen = 0
 
 

@@ -1,6 +1,8 @@
 // Optimizer, weight packing, input layout and error plumbing for libavt.
 //  * Adam with coupled L2 weight decay over one flat fp32 buffer (torch.optim.Adam semantics as
 //    constructed at train_hardway_1frame.py:116 and stepped at :134).
+//  * SGD with momentum / dampening / weight decay / nesterov over the same kind of buffer (torch.optim.SGD: the
+//    R3D fine-tuning recipe's optimizer).
 //  * Weight packing: fp32 master weights (OHWI memory order, i.e. channels_last OIHW params) ->
 //    bf16 fwd operand [K][Kg] (stem channels padded) and bf16 dgrad operand [C][R*S*K].
 //  * Input layout: fp32 NCHW (the reference's frames.float()/spec.float(), train_hardway_1frame.py:129)
@@ -340,6 +342,56 @@ __global__ void adam_prep_kernel(int* __restrict__ step, const float* __restrict
   coef[5] = hyper[4];
 }
 
+// torch.optim.SGD (maximize=False) over one flat segment, hyper-parameters and step count on the device:
+// hyper = {lr, momentum, dampening, weight_decay, nesterov (0 / 1)}.  g = grad * gscale + wd * p; with momentum
+// (buf given and momentum != 0) buf = g at the first step (*step == 0 on entry), buf = mu * buf + (1 - dampening) * g
+// afterwards, g = g + mu * buf (nesterov) or buf; p -= lr * g.  Without momentum buf is neither read nor written.
+constexpr int kSgdGridCap = 2048;  // blocks; a thread then walks its 16-byte vectors in a grid-stride loop
+
+__device__ __forceinline__ float sgd_update(float p, float gr, float* b, bool use_buf, bool first, float gscale, float lr,
+                                            float mu, float keep, float wd, bool nesterov) {
+  float g = gr * gscale + wd * p;
+  if (use_buf) {
+    const float nb = first ? g : mu * *b + keep * g;
+    *b = nb;
+    g = nesterov ? g + mu * nb : nb;
+  }
+  return p - lr * g;
+}
+
+__global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                  float* __restrict__ buf, long long n, float gscale,
+                                                  const float* __restrict__ hyper, const int* __restrict__ step) {
+  const float lr = hyper[0], mu = hyper[1], keep = 1.f - hyper[2], wd = hyper[3];
+  const bool nesterov = hyper[4] != 0.f;
+  const bool use_buf = buf != nullptr && mu != 0.f;
+  const bool first = *step == 0;
+  const long long nv = n / 4;
+  for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < nv; i += (long long)gridDim.x * blockDim.x) {
+    f32x4 pp = reinterpret_cast<f32x4*>(p)[i];
+    const f32x4 gg = reinterpret_cast<const f32x4*>(g)[i];
+    f32x4 bb = {0.f, 0.f, 0.f, 0.f};
+    if (use_buf && !first) bb = reinterpret_cast<f32x4*>(buf)[i];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      float b = bb[e];
+      pp[e] = sgd_update(pp[e], gg[e], &b, use_buf, first, gscale, lr, mu, keep, wd, nesterov);
+      bb[e] = b;
+    }
+    reinterpret_cast<f32x4*>(p)[i] = pp;
+    if (use_buf) reinterpret_cast<f32x4*>(buf)[i] = bb;
+  }
+  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {  // tail
+    const long long i = nv * 4 + threadIdx.x;
+    float b = (use_buf && !first) ? buf[i] : 0.f;
+    p[i] = sgd_update(p[i], g[i], &b, use_buf, first, gscale, lr, mu, keep, wd, nesterov);
+    if (use_buf) buf[i] = b;
+  }
+}
+
+// after sgd_kernel on the same stream: the step is counted once every block has read the old count
+__global__ void sgd_count_kernel(int* __restrict__ step) { *step = *step + 1; }
+
 static int grid_for(long long n) {
   long long b = (n + 255) / 256;
   if (b > 8192) b = 8192;
@@ -631,6 +683,26 @@ extern "C" int avt_adam_apply_dev(float* param, const float* grad, float* exp_av
   hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n / 4 + 1)), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg,
                      exp_avg_sq, n, grad_scale, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, coef);
   return check_launch("adam_apply_dev");
+}
+
+// torch.optim.SGD(lr, momentum, dampening, weight_decay, nesterov) on one flat segment, graph-capturable as
+// avt_adam_step_dev is: hyper = device float[AVT_SGD_HYPER_FLOATS] read at every launch, *step the device count of
+// steps taken (0 before the first: that step sets buf = g), incremented by a second launch behind the update.
+// buf == NULL: plain SGD whatever hyper[1] holds.
+extern "C" int avt_sgd_step_dev(float* param, const float* grad, float* buf, long long n, float grad_scale,
+                                const float* hyper, int* step, void* stream) {
+  AVT_REQUIRE(param && grad && hyper && step, "sgd_step_dev: null pointer");
+  AVT_REQUIRE(n >= 0, "sgd_step_dev: negative size");
+  AVT_REQUIRE(((uintptr_t)param | (uintptr_t)grad | (uintptr_t)buf) % 16 == 0,
+              "sgd_step_dev: buffers must be 16-byte aligned");
+  if (n == 0) return AVT_OK;
+  hipStream_t st = (hipStream_t)stream;
+  long long blocks = (n / 4 + 256) / 256;
+  if (blocks > kSgdGridCap) blocks = kSgdGridCap;
+  hipLaunchKernelGGL(sgd_kernel, dim3((unsigned)blocks), dim3(256), 0, st, param, grad, buf, n, grad_scale, hyper,
+                     (const int*)step);
+  hipLaunchKernelGGL(sgd_count_kernel, dim3(1), dim3(1), 0, st, step);
+  return check_launch("sgd_step_dev");
 }
 
 extern "C" int avt_nchw_to_nhwc_bf16(const float* x, void* y, int N, int C, int H, int W, int Cp, void* stream) {

@@ -1,4 +1,4 @@
-"""Fused Adam over an AVENet's flat parameter buffer (libavt ``avt_adam_step``).
+"""Fused Adam over an AVENet's flat parameter buffer (libavt ``avt_adam_step``), and the flat SGD of the R3D step.
 
 Drop-in for ``torch.optim.Adam(model.parameters(), lr, weight_decay=wd)`` as used at
 train_hardway_1frame.py:116/134 (betas (0.9, 0.999), eps 1e-8, coupled L2 decay, amsgrad off).
@@ -6,7 +6,7 @@ Parameters whose ``.grad`` is None are skipped, exactly like torch.
 """
 from __future__ import annotations
 
-from typing import Dict, Optional
+from typing import Dict, Optional, Union
 
 import torch
 
@@ -139,9 +139,103 @@ class FlatAdam:
              P(self.exp_avg_sq[lo:]), hi - lo, grad_scale, P(self._coef), stream_ptr())
 
 
+class FlatSGD:
+    """torch.optim.SGD state for the trainable region of a FlatStore (libavt ``avt_sgd_step_dev``): the optimizer of
+    the R3D fine-tuning recipe (SGD, momentum 0.9, weight decay 1e-3) for train.R3DTrainStep.  FlatAdam's surface:
+    ``lr`` / ``set_lr``, ``initial_lr``, ``t``, ``step(gflat, grad_scale)``; the hyper-parameters and the step count
+    live on the device and the setters are stream-ordered device writes, so a captured step follows a schedule
+    (FlatMultiStepLR) or a restored checkpoint.  With momentum 0 no buffer is kept, and momentum cannot be turned on
+    later.  nesterov needs momentum > 0 and dampening 0, as torch's does."""
+
+    _HYPER = ("lr", "momentum", "dampening", "wd", "nesterov")
+
+    def __init__(self, flat, lr=1e-2, momentum=0.9, dampening=0.0, weight_decay=1e-3, nesterov=False):
+        check_sgd_hyper(lr, momentum, dampening, weight_decay, nesterov)
+        self.flat = flat
+        dev = flat.flat.device
+        self.momentum_buffer = (torch.zeros(flat.n_train, device=dev, dtype=torch.float32) if momentum != 0 else None)
+        self.t_dev = torch.zeros(1, device=dev, dtype=torch.int32)
+        self._host = {"lr": float(lr), "momentum": float(momentum), "dampening": float(dampening),
+                      "wd": float(weight_decay), "nesterov": float(bool(nesterov))}
+        self.initial_lr = None  # set by the first scheduler, saved in checkpoints (torch's group 'initial_lr')
+        self._hyper = torch.tensor([self._host[k] for k in self._HYPER], device=dev, dtype=torch.float32)
+
+    def _set(self, key: str, value: float):
+        h = dict(self._host, **{key: float(value)})
+        check_sgd_hyper(h["lr"], h["momentum"], h["dampening"], h["wd"], bool(h["nesterov"]))
+        if key == "momentum" and value != 0 and self.momentum_buffer is None:
+            raise ValueError("avt FlatSGD: built with momentum 0 (no buffer); build a new one to use momentum")
+        self._host = h
+        self._hyper[self._HYPER.index(key)] = float(value)  # stream-ordered: later launches and replays read it
+
+    @property
+    def lr(self) -> float:
+        return self._host["lr"]
+
+    @lr.setter
+    def lr(self, v: float):
+        self._set("lr", v)
+
+    def set_lr(self, v: float):
+        self._set("lr", v)
+
+    @property
+    def momentum(self) -> float:
+        return self._host["momentum"]
+
+    @momentum.setter
+    def momentum(self, v: float):
+        self._set("momentum", v)
+
+    @property
+    def dampening(self) -> float:
+        return self._host["dampening"]
+
+    @dampening.setter
+    def dampening(self, v: float):
+        self._set("dampening", v)
+
+    @property
+    def wd(self) -> float:
+        return self._host["wd"]
+
+    @wd.setter
+    def wd(self, v: float):
+        self._set("wd", v)
+
+    @property
+    def nesterov(self) -> bool:
+        return bool(self._host["nesterov"])
+
+    @nesterov.setter
+    def nesterov(self, v: bool):
+        self._set("nesterov", float(bool(v)))
+
+    @property
+    def t(self) -> int:
+        """Steps taken (host read: synchronises)."""
+        return int(self.t_dev.item())
+
+    def step(self, gflat: torch.Tensor, grad_scale: float = 1.0):
+        call("avt_sgd_step_dev", P(self.flat.flat), P(gflat), P(self.momentum_buffer), self.flat.n_train, grad_scale,
+             P(self._hyper), P(self.t_dev), stream_ptr())
+
+
+def check_sgd_hyper(lr, momentum, dampening, weight_decay, nesterov) -> None:
+    """torch.optim.SGD's constructor checks."""
+    if lr < 0.0:
+        raise ValueError(f"Invalid learning rate: {lr}")
+    if momentum < 0.0:
+        raise ValueError(f"Invalid momentum value: {momentum}")
+    if weight_decay < 0.0:
+        raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+    if nesterov and (momentum <= 0 or dampening != 0):
+        raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+
+
 class FlatMultiStepLR:
     """torch.optim.lr_scheduler.MultiStepLR (train_hardway_1frame.py:118: milestones [60,100,150,180],
-    gamma 0.1, stepped once per epoch at :138) for a FlatAdam: lr = base_lr * gamma^(number of
+    gamma 0.1, stepped once per epoch at :138) for a FlatAdam or a FlatSGD: lr = base_lr * gamma^(number of
     milestones <= epoch).  Writes the device hyper-parameter, so captured step graphs follow.
 
     base_lr is the optimizer's lr for a fresh schedule (last_epoch = -1; recorded as opt.initial_lr,
@@ -151,7 +245,7 @@ class FlatMultiStepLR:
     the restored lr is kept and the decay never applied twice; later epochs follow the uninterrupted
     schedule (torch's chainable form multiplies the restored lr at each later milestone: the same)."""
 
-    def __init__(self, opt: FlatAdam, milestones, gamma: float = 0.1, last_epoch: int = -1,
+    def __init__(self, opt: Union[FlatAdam, FlatSGD], milestones, gamma: float = 0.1, last_epoch: int = -1,
                  base_lr: Optional[float] = None):
         self.opt = opt
         self.milestones = sorted(int(m) for m in milestones)

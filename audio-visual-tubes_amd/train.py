@@ -29,7 +29,7 @@ import torch.distributed as dist
 
 from ._lib import note_param_write
 from .engine import AVEngine
-from .optim import FlatAdam
+from .optim import FlatAdam, FlatSGD
 
 
 def world_size(pg: Optional[dist.ProcessGroup] = None) -> int:
@@ -326,3 +326,123 @@ class TwoViewTrainStep(HardWayTrainStep):
         self.grad.zero_()
         self.engine.backward(tape, (out["dlogits"], out["dwA"]), self.grad, on_boundary)
         return out["losses"]
+
+
+class R3DTrainStep:
+    """Fused fine-tuning step of a stand-alone R3D-18 (``resnet3D.generate_model(18, n_classes=...)``): what
+    ``loss = F.cross_entropy(net(video), labels); loss.backward(); opt.step()`` computes, issued as libavt launches
+    into one flat gradient buffer -- R3DTrunk's taped forward, the classifier head (avt_cls_pool_fwd, avt_cls_fc_fwd,
+    avt_softmax_ce and their backward), R3DTrunk.backward, one flat optimizer launch -- with no autograd graph, no
+    per-parameter optimizer loop and no per-step gradient allocation, and capturable into one HIP graph.
+
+    ``optimizer`` is "sgd" (optim.FlatSGD: torch.optim.SGD, the R3D recipe's optimizer; ``hyper`` = lr, momentum,
+    dampening, weight_decay, nesterov) or "adam" (optim.FlatAdam; lr, betas, eps, weight_decay); ``self.opt`` takes a
+    FlatMultiStepLR and checkpoint.save_checkpoint / load_checkpoint.  ``step(video, labels)`` returns the mean CE loss
+    over the rows whose label lies in [0, n_classes) (others are ignored rows, as ignore_index = -100) as a device
+    scalar, without a host sync; ``self.correct`` (int32 [1]) and ``self.logits`` are that step's top-1 count and
+    logits on the device.  ``capture(video, labels)`` / replay follow HardWayTrainStep: the arguments become the static
+    inputs, later steps copy theirs in, a batch of another shape runs eagerly.
+
+    The constructor calls ``net.enable_backward()`` and refuses a trunk owned by a FullModel (FullModel.
+    enable_video_backward trains that one), a parameter with requires_grad False (partial freezing is not fused), an
+    eval-mode trunk and a process group: one GPU only.  ``net(video)`` under autograd keeps working alongside (its own
+    engine over the same flat storage)."""
+
+    def __init__(self, net, optimizer: str = "sgd", process_group: Optional[dist.ProcessGroup] = None, **hyper):
+        from .resnet3D import ResNet
+        from .tube import R3DEngine
+
+        if not isinstance(net, ResNet):
+            raise TypeError("avt R3DTrainStep: expected a resnet3D.ResNet (generate_model(18, ...))")
+        if process_group is not None or world_size() > 1:
+            raise NotImplementedError("avt R3DTrainStep: single GPU only (no process group); data-parallel "
+                                      "fine-tuning of the stand-alone trunk is not built")
+        if net._avt_parent is not None:
+            raise RuntimeError("avt R3DTrainStep: this trunk belongs to a FullModel; train it from the model's loss "
+                               "(FullModel.enable_video_backward() + HardWayTrainStep)")
+        frozen = [n for n, p in net.named_parameters() if not p.requires_grad]
+        if frozen:
+            raise NotImplementedError(f"avt R3DTrainStep: every parameter must require grad (partial freezing is not "
+                                      f"fused); frozen: {frozen[:3]}{' ...' if len(frozen) > 3 else ''}")
+        if not net.training:
+            raise RuntimeError("avt R3DTrainStep: the trunk is in eval mode; call net.train() (the step updates the "
+                               "BatchNorm statistics)")
+        net.enable_backward()
+        self.net = net
+        self.flat = net._flat_store()
+        if not self.flat.flat.is_cuda:
+            raise RuntimeError("avt R3DTrainStep: move the trunk to the GPU first (no CPU path)")
+        self.engine = R3DEngine(self.flat, "", max_pool=not net.no_max_pool, with_backward=True)
+        if optimizer == "sgd":
+            self.opt = FlatSGD(self.flat, **hyper)
+        elif optimizer == "adam":
+            self.opt = FlatAdam(self.flat, **hyper)
+        else:
+            raise ValueError(f"avt R3DTrainStep: optimizer must be 'sgd' or 'adam', got {optimizer!r}")
+        self.grad = torch.zeros(self.flat.n_train, device=self.flat.flat.device, dtype=torch.float32)
+        self.correct = torch.zeros(1, device=self.grad.device, dtype=torch.int32)
+        self.logits = None
+        self._graph = None
+        self._stepped = False
+
+    def _fused(self, video: torch.Tensor, labels: torch.Tensor):
+        out, tape = self.engine.forward_cls(video, labels, training=True)
+        self.grad.zero_()
+        self.engine.backward_cls(tape, self.grad)
+        self.opt.step(self.grad, grad_scale=1.0)
+        return out
+
+    def _check(self):
+        if not self.net.training:
+            raise RuntimeError("avt R3DTrainStep: the trunk is in eval mode; call net.train()")
+        if self.net._flat_store() is not self.flat or self.engine.flat.flat is not self.flat.flat:
+            raise RuntimeError("avt R3DTrainStep: the trunk's storage changed (moved or rebuilt) since the step was "
+                               "built; build a new step")
+
+    def _eager_step(self, video: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
+        self._check()
+        out = self._fused(video, labels)
+        self.correct, self.logits = out["correct"], out["logits"]
+        self._stepped = True
+        return out["loss"][0]
+
+    def step(self, video: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
+        """One fine-tuning step; returns the mean CE loss (device scalar, no host sync)."""
+        if self._graph is not None:
+            return self._replay(video, labels)
+        return self._eager_step(video, labels)
+
+    def capture(self, video: torch.Tensor, labels: torch.Tensor) -> None:
+        """Record one step into a HIP graph; later ``step`` calls replay it (HardWayTrainStep.capture's contract:
+        after at least one eager step; capture itself does not change the training state).  ``video`` / ``labels``
+        (int64) become the static inputs."""
+        self._check()
+        if not self._stepped:
+            raise RuntimeError("avt R3DTrainStep: run one eager step before capture() (the engine allocates its "
+                               "persistent buffers at first use)")
+        if not video.is_cuda or not labels.is_cuda:
+            raise RuntimeError("avt: inputs must be on the GPU (no CPU path)")
+        if labels.dtype != torch.long or not labels.is_contiguous():
+            raise TypeError("avt R3DTrainStep.capture: labels must be a contiguous int64 tensor (the static input)")
+        torch.cuda.synchronize()
+        self._static_in = (video, labels)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            out = self._fused(video, labels)
+        self._static_out = out
+        self._graph = g
+
+    def _replay(self, video: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
+        if any(tuple(x.shape) != tuple(s.shape) for s, x in zip(self._static_in, (video, labels))):
+            return self._eager_step(video, labels)  # e.g. the short last batch of an epoch
+        self._check()
+        if not video.is_cuda or not labels.is_cuda:
+            raise RuntimeError("avt: inputs must be on the GPU (no CPU path)")
+        for s, x in zip(self._static_in, (video, labels)):
+            if x is not s:
+                s.copy_(x)
+        note_param_write()  # the replayed launches update weights and running statistics (folded inference: _lib.py)
+        self._graph.replay()
+        out = self._static_out
+        self.correct, self.logits = out["correct"], out["logits"]
+        return out["loss"][0]

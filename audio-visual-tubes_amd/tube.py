@@ -754,3 +754,62 @@ class R3DEngine(AVEngine):
         finally:
             self.store.grads = None
         return gvideo
+
+    # ------------------------------------------------------------------ the classifier step, all on libavt
+    def forward_cls(self, video: torch.Tensor, labels: torch.Tensor, training: bool = True, ce_scale: float = 1.0):
+        """video fp32 [b,3,t,H,W], labels int64 [b] -> (out, tape): the trunk's taped forward, then the head on the
+        device -- avt_cls_pool_fwd, avt_cls_fc_fwd, avt_softmax_ce (resnet3D.py:208-212 + nn.CrossEntropyLoss; a label
+        outside [0, n_classes) is an ignored row).  out = {"loss": [1], "logits": [b, n], "dlogits": [b, n],
+        "correct": int32 [1]}, device tensors, no host sync; the tape also carries what ``backward_cls`` reads.
+        ``forward`` / ``backward`` (the torch head under autograd) are not involved and keep their launch sequence."""
+        if not video.is_cuda or not labels.is_cuda:
+            raise RuntimeError("avt: inputs must be on the GPU (no CPU path)")
+        if video.dim() != 5:
+            raise ValueError(f"avt: expected video [b,3,t,H,W], got {tuple(video.shape)}")
+        b = video.shape[0]
+        if labels.dim() != 1 or labels.shape[0] != b or labels.is_floating_point():
+            raise ValueError(f"avt: expected {b} integer class labels, got {tuple(labels.shape)} {labels.dtype}")
+        if not self.with_backward:
+            raise RuntimeError("avt: this R3D engine was built forward-only")
+        labels = labels.to(torch.long).contiguous()
+        self.pack_weights()
+        if training and self._nbt_idx.numel():
+            self.flat.nbt.index_add_(0, self._nbt_idx, torch.ones_like(self._nbt_idx))
+        w, bias = self.flat.raw(self._prefix + "fc.weight"), self.flat.raw(self._prefix + "fc.bias")
+        v, tp = self.vid.forward(video, self.store, training, tape=True)  # [(b t), h, w, 512] bf16
+        dev, C, n = v.device, v.shape[-1], w.shape[0]
+        per = v.numel() // (b * C)  # positions the average pool spans per clip
+        wsb = int(query("avt_cls_pool_ws_bytes", b, per, C))
+        ws = torch.empty(max(wsb, 16), device=dev, dtype=torch.uint8)
+        feat = torch.empty(b, C, device=dev, dtype=torch.float32)
+        call("avt_cls_pool_fwd", P(v), P(feat), b, per, C, P(ws), wsb, stream_ptr())
+        logits = torch.empty(b, n, device=dev, dtype=torch.float32)
+        call("avt_cls_fc_fwd", P(feat), P(w), P(bias), P(logits), b, C, n, stream_ptr())
+        loss = torch.empty(1, device=dev, dtype=torch.float32)
+        dlogits = torch.empty_like(logits)
+        correct = torch.empty(1, device=dev, dtype=torch.int32)
+        call("avt_softmax_ce", P(logits), P(labels), b, n, ce_scale, P(loss), P(dlogits), P(correct), stream_ptr())
+        tp.update(v_shape=tuple(v.shape), feat=feat, training=training, video_shape=tuple(video.shape),
+                  stem_dgrad=False, dlogits=dlogits, labels=labels)
+        return {"loss": loss, "logits": logits, "dlogits": dlogits, "correct": correct}, tp
+
+    def backward_cls(self, tape, gflat: torch.Tensor) -> None:
+        """The backward of ``forward_cls`` from its tape: avt_cls_fc_bwd stores the fc gradients into their slots of
+        the flat buffer gflat[:n_train] and yields d(loss)/d(features), avt_cls_pool_bwd broadcasts it over the layer4
+        map, R3DTrunk.backward accumulates every other gradient (gflat zeroed by the caller), in the mode (train /
+        eval BatchNorm) of the forward that made the tape."""
+        grads = self.flat.grad_views(gflat)
+        feat, dlogits = tape["feat"], tape["dlogits"]
+        w = self.flat.raw(self._prefix + "fc.weight")
+        b, C = feat.shape
+        n = w.shape[0]
+        gfeat = torch.empty_like(feat)
+        call("avt_cls_fc_bwd", P(dlogits), P(feat), P(w), P(grads[self._prefix + "fc.weight"]),
+             P(grads[self._prefix + "fc.bias"]), P(gfeat), b, C, n, stream_ptr())
+        g = torch.empty(tape["v_shape"], device=feat.device, dtype=torch.bfloat16)
+        call("avt_cls_pool_bwd", P(gfeat), P(g), b, g.numel() // (b * C), C, stream_ptr())
+        self.store.grads = grads
+        try:
+            self.vid.backward(tape, g, self.store, training=tape.get("training", True))
+        finally:
+            self.store.grads = None

@@ -29,6 +29,11 @@
  *                                HardWayAttention.forward (model.py:46-60)
  *   avt_hardway_ce               nn.CrossEntropyLoss()(logits, zeros) (train_hardway_1frame.py:113, 130-131)
  *   avt_adam_step                torch.optim.Adam(lr, weight_decay) step (train_hardway_1frame.py:116, 134)
+ *   avt_sgd_step_dev             torch.optim.SGD(lr, momentum, dampening, weight_decay, nesterov) step: the optimizer
+ *                                of the R3D fine-tuning recipe whose weights train_3D.py:89 loads
+ *   avt_cls_pool_fwd/bwd,        the R3D-18's own head, ResNet.forward's avgpool -> view -> fc
+ *   avt_cls_fc_fwd/bwd,          (models/resnet3D.py:208-212), with nn.CrossEntropyLoss on class labels and their
+ *   avt_softmax_ce               backward: the fused fine-tuning step of a stand-alone trunk (train.R3DTrainStep)
  *   avt_conv3d_fwd               nn.Conv3d fwd of the R3D-18 video trunk (models/resnet3D.py:14-28 conv3x3x3 /
  *                                conv1x1x1, called from BasicBlock.forward 45-61; FullModel.vidnet, model.py:20)
  *   avt_video_stem_im2col,       the R3D stem Conv3d(3,64,(7,7,7),s(1,2,2),p3) (models/resnet3D.py:122-127) as a
@@ -454,6 +459,40 @@ int avt_npratio_loss(const float* x, int b, int t, int P, float* loss, float* dx
 int avt_flip_l1_loss(const float* x, const float* y, long long rows, int W, float* loss, float* dx, float* dy,
                      float* ws, void* stream);
 
+/* ---- classifier head of the stand-alone R3D-18: AdaptiveAvgPool3d((1,1,1)) + fc + CrossEntropyLoss ----
+ * (models/resnet3D.py:208-212 `x = self.avgpool(x); x = x.view(x.size(0), -1); x = self.fc(x)` and the class-label loss
+ * of the fine-tuning recipe the trunk's Kinetics weights come from, train_3D.py:89).  fp32 throughout except the layer4
+ * map and its gradient (bf16).  Every sum runs in a fixed order, no atomics: identical inputs give identical bits.
+ *
+ * avt_cls_pool_fwd: v bf16 [b][per][C] (the layer4 map, per = t*h*w, C % 8 == 0, 16-byte aligned) -> feat fp32 [b][C] =
+ * (sum_p v[b][p][c]) / per.  DIVIDE BY per: the fp32 sum is divided by (float)per with IEEE fp32 division (correctly
+ * rounded); no reciprocal is formed, here or in avt_cls_pool_bwd.  `per` is split into slots of 64 rows, one block per
+ * (slot, clip, 512 channels); each slot's partial sums are written to the workspace with plain stores and a second
+ * launch adds them in slot order.  workspace: avt_cls_pool_ws_bytes(b, per, C) = b * ceil(per / 64) * C * 4 bytes, any
+ * contents; NULL or a shorter one is AVT_EINVAL.  1 <= per < 2^24, b <= 65535. */
+size_t avt_cls_pool_ws_bytes(int b, long long per, int C);
+int avt_cls_pool_fwd(const void* v, float* feat, int b, long long per, int C, void* workspace, size_t ws_bytes,
+                     void* stream);
+/* g bf16 [b][per][C] = bf16_rne(gfeat[b][c] / per) at every position p (the same fp32 division), 16-byte stores */
+int avt_cls_pool_bwd(const float* gfeat, void* g, int b, long long per, int C, void* stream);
+/* nn.Linear: logits[b][n] = bias[n] + sum_c feat[b][c] * W[n][c]; W row-major [n][C] (the Parameter's layout), any
+ * n >= 1, C >= 1.  One wave per output: lanes strided over c, then the xor-butterfly wave sum, then + bias. */
+int avt_cls_fc_fwd(const float* feat, const float* W, const float* bias, float* logits, int b, int C, int n,
+                   void* stream);
+/* Its backward, stored (not accumulated): gW[n][C] = sum_b dlogits[b][n] * feat[b][c] and gbias[n] = sum_b
+ * dlogits[b][n] (b increasing), gfeat[b][C] = sum_n dlogits[b][n] * W[n][c] (n increasing).  Two launches. */
+int avt_cls_fc_bwd(const float* dlogits, const float* feat, const float* W, float* gW, float* gbias, float* gfeat, int b,
+                   int C, int n, void* stream);
+/* nn.CrossEntropyLoss()(logits, labels) * scale, its gradient and the top-1 count: logits fp32 [b][n], labels int64
+ * [b] (device).  A label outside [0, n) marks an ignored row, as torch's ignore_index = -100 does for -100: it adds
+ * nothing to the loss, its dlogits row is +0 and it does not count in the denominator; the kernel never traps on a
+ * label.  loss[0] = scale * mean over the valid rows of (logsumexp(z) - z[label]); dlogits[b][n] (optional) = scale *
+ * (softmax(z) - onehot(label)) / (valid rows); correct[0] (optional, int32) = valid rows whose argmax (the lowest index
+ * among equal maxima) is the label.  With NO valid row the loss and every gradient are 0 (torch returns NaN there).
+ * One block: a wave per row, rows wider than the wave in strided passes; rows and waves are summed in index order. */
+int avt_softmax_ce(const float* logits, const long long* labels, int b, int n, float scale, float* loss, float* dlogits,
+                   int* correct, void* stream);
+
 /* ---- localisation metrics (test loops of train_hardway*.py / test.py; utils.py:203-239, 311-318) ---- */
 /* A [N][h][w] heatmaps -> cv2 INTER_LINEAR resize to S x S, normalize_img(-.), 1 - ., median
  * binarisation, cIoU(., gt, 0.5): out [N][3] fp64 = (cIoU, intersection, denominator) when gt
@@ -549,6 +588,16 @@ int avt_adam_step_dev(float* param, const float* grad, float* exp_avg, float* ex
 int avt_adam_prep_dev(const float* hyper, int* step, float* coef, void* stream);
 int avt_adam_apply_dev(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long long n,
                        float grad_scale, const float* coef, void* stream);
+/* torch.optim.SGD (maximize=False) over one flat region, with the hyper-parameters and the step count on the device as
+ * in avt_adam_step_dev: hyper = device float[AVT_SGD_HYPER_FLOATS] {lr, momentum, dampening, weight_decay, nesterov
+ * (0 / 1)}, read at every launch (a schedule writes it; a captured graph follows); *step = steps taken so far, read by
+ * the update and incremented by a second launch behind it.  g = grad * grad_scale + weight_decay * p; with momentum:
+ * buf = g at the first step (*step == 0 on entry), afterwards buf = momentum * buf + (1 - dampening) * g, then
+ * g = g + momentum * buf (nesterov) or g = buf; p -= lr * g.  With momentum 0 -- or buf == NULL, which means plain SGD
+ * whatever hyper[1] holds -- buf is neither read nor written.  param / grad / buf 16-byte aligned; any n >= 0. */
+#define AVT_SGD_HYPER_FLOATS 5
+int avt_sgd_step_dev(float* param, const float* grad, float* buf, long long n, float grad_scale, const float* hyper,
+                     int* step, void* stream);
 int avt_pack_conv_weight(const float* w, int K, int R, int S, int C, int Cp, int Kg, void* out_fwd, void* out_dgrad,
                          void* stream);
 /* two launches (fwd copy, dgrad transpose) for many convs: descs = device array of n records
