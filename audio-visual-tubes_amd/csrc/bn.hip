@@ -14,6 +14,14 @@
 //         avt_bn_relu_bwd recomputes the ReLU mask from (xc, scale, shift) instead of reading y
 //         (BasicBlock.bn1, base_models.py:47-48); the stem's bn1+relu+maxpool is fused both ways
 //         (avt_stem_*, below) so its full-resolution activation is never stored.
+//
+//   Layout of this file: the finalize kernels; then the shared pieces -- the constants' two policies (Reg8 / Mem8),
+//   each formula once (bn_fwd8, relu_mask8, bn_bwd8, bn_reduce8), the row walker (walk_rows) and the reduces' block
+//   epilogue (block_sums_to_slot); then the kernels, which only pick a walk (grid-stride or rows), a policy and the
+//   formulas; the stem kernels (their own walk); the host launchers (reduce_deal, bn_bwd_finalize_launch,
+//   with_mask_form) and the entry points.  A change to a formula or to the walk is made in one place.
+#include <type_traits>
+
 #include "avt_common.h"
 
 namespace avt {
@@ -112,17 +120,46 @@ __global__ __launch_bounds__(kFinThreads) void bn_finalize_kernel(double* __rest
   }
 }
 
-// out = [relu]( x*scale + shift + [residual*rscale + rshift | residual] )
-// The channel block of vector i is i % (C/8); POW2 (C/8 a power of two) takes it as a bit mask.
-// This grid-stride form re-reads the per-channel constants for every vector: L1 hits, but each one is a
-// vector-memory instruction beside the 1-3 data loads (4-14 of them per 16-byte vector produced), and with one
-// thread per vector there is nothing to hoist them out of.  It is the kernel of a C/8 that does not divide 256
-// (POW2 = false) and of AVT_BN_EW=0; every trunk shape takes the row-walking form below (bn_apply_rw_kernel),
-// which reads the constants once per thread -- measured in profiles/bn_rowwalk_kernel_stats_b128.txt.
-template <bool POW2>
-__device__ __forceinline__ int chan_block(long long i, int cv) {
-  return POW2 ? (int)((unsigned)i & (unsigned)(cv - 1)) : (int)(i % cv);
-}
+// ---------------------------------------------------------------------------------------------
+// The pieces every elementwise pass and every reduce below is put together from: one row walker, each formula once.
+
+__device__ __forceinline__ u32x4 ld8(const bf16_t* p, size_t o) { return reinterpret_cast<const u32x4*>(p)[o]; }
+__device__ __forceinline__ void st8(bf16_t* p, size_t o, const u32x4& v) { reinterpret_cast<u32x4*>(p)[o] = v; }
+
+// The eight per-channel constants of a thread's channel chunk [c0, c0 + 8), by how they are reached.  Reg8: loaded
+// once, into registers -- a row-walking thread keeps its chunk.  Mem8: read from memory at every use -- a grid-stride
+// thread changes chunk with every vector, so there is nothing to hoist them out of (L1 hits, but each one a
+// vector-memory instruction beside the 1-3 data loads).  The formulas are templates over the two, so the grid-stride
+// kernels and their row-walking twins evaluate the same expression in the same order: the same bits.
+struct Reg8 {
+  float v[8];
+  static __device__ __forceinline__ Reg8 at(const float* p, int c0) {
+    Reg8 k;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) k.v[e] = p[c0 + e];
+    return k;
+  }
+  __device__ __forceinline__ float operator[](int e) const { return v[e]; }
+  using Prod = Reg8;  // a[e] * b[e], taken once
+  static __device__ __forceinline__ Prod prod(const Reg8& a, const Reg8& b) {
+    Reg8 k;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) k.v[e] = a[e] * b[e];
+    return k;
+  }
+};
+struct Mem8 {
+  const float* p;
+  int c0;
+  static __device__ __forceinline__ Mem8 at(const float* p, int c0) { return {p, c0}; }
+  __device__ __forceinline__ float operator[](int e) const { return p[c0 + e]; }
+  struct Prod {  // a[e] * b[e], taken at every use
+    const float *a, *b;
+    int c0;
+    __device__ __forceinline__ float operator[](int e) const { return a[c0 + e] * b[c0 + e]; }
+  };
+  static __device__ __forceinline__ Prod prod(const Mem8& a, const Mem8& b) { return {a.p, b.p, a.c0}; }
+};
 
 // Bit e of the result: bf16 element e of v is > 0 (positive and non-zero as int16) -- the ReLU
 // backward's `result > 0` evaluated on the stored output.
@@ -137,6 +174,187 @@ __device__ __forceinline__ unsigned pos_bits8(const u32x4& v) {
   return b;
 }
 
+// Forward: out = [relu]( x*scale + shift + [residual*rscale + rshift | residual] ).  res: 0 no residual, 1 + residual,
+// 2 + residual*rscale + rshift.
+template <class K>
+__device__ __forceinline__ u32x4 bn_fwd8(const u32x4& xq, const u32x4& rq, int res, bool relu, const K& sc, const K& sh,
+                                         const K& rs, const K& rh) {
+  float f[8];
+  unpack8(xq, f);
+#pragma unroll
+  for (int e = 0; e < 8; ++e) f[e] = __builtin_fmaf(f[e], sc[e], sh[e]);
+  if (res) {
+    float r[8];
+    unpack8(rq, r);
+    if (res == 2) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) f[e] += r[e] * rs[e] + rh[e];
+    } else {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) f[e] += r[e];
+    }
+  }
+  if (relu) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) f[e] = fmaxf(f[e], 0.f);
+  }
+  return pack8(f);
+}
+
+// One row-vector of a backward pass as loaded: g, the pre-activation xc and whichever of the others the pass reads
+// (a null pointer: not loaded, the member left as it is) -- the saved output y, the mask byte, a second BN's pre-activation.
+struct BwdRow {
+  u32x4 g, x, y, x2;
+  unsigned bits;
+};
+__device__ __forceinline__ void load_bwd_row(BwdRow& v, const bf16_t* g, const bf16_t* xc, const bf16_t* y,
+                                             const unsigned char* mk, const bf16_t* xc2, size_t o) {
+  v.g = ld8(g, o);
+  v.x = ld8(xc, o);
+  if (y) v.y = ld8(y, o);
+  if (xc2) v.x2 = ld8(xc2, o);
+  if (mk) v.bits = mk[o];
+}
+
+// The ReLU mask of the backward pass, g' = g * [output > 0], in its four forms: none (g is g' already); the saved
+// output, y > 0; recomputed from the pre-activation, relu(fma(xc, mscale, mshift)) > 0 -- the exact expression the
+// forward evaluated, so the mask is identical without reading y; the bits avt_bn_apply_mask stored.
+enum { kMaskNone = 0, kMaskY = 1, kMaskFma = 2, kMaskBits = 3 };
+__host__ __device__ inline int mask_form(const void* y, const float* mscale) {
+  return y ? kMaskY : mscale ? kMaskFma : kMaskNone;
+}
+template <class K = Reg8>
+__device__ __forceinline__ void relu_mask8(int form, float* gg, const float* xx, const BwdRow& v, const K& ms = K{},
+                                           const K& mh = K{}) {
+  if (form == kMaskY) {
+    float yy[8];
+    unpack8(v.y, yy);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) gg[e] = yy[e] > 0.f ? gg[e] : 0.f;
+  } else if (form == kMaskFma) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) gg[e] = __builtin_fmaf(xx[e], ms[e], mh[e]) > 0.f ? gg[e] : 0.f;
+  } else if (form == kMaskBits) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) gg[e] = (v.bits >> e) & 1u ? gg[e] : 0.f;
+  }
+}
+
+// Backward apply: g_c = gamma*invstd*(g' - k1 - xhat*k2), xhat = (xc - mean)*invstd.
+template <class K>
+struct BwdK {
+  K mu, is;
+  typename K::Prod gi;  // gamma*invstd
+  K k1, k2;
+  static __device__ __forceinline__ BwdK at(const float* mean, const float* invstd, const float* gamma, const float* k1,
+                                            const float* k2, int c0) {
+    const K is = K::at(invstd, c0);
+    return {K::at(mean, c0), is, K::prod(K::at(gamma, c0), is), K::at(k1, c0), K::at(k2, c0)};
+  }
+};
+template <class K>
+__device__ __forceinline__ u32x4 bn_bwd8(const float* gg, const float* xx, const BwdK<K>& k) {
+  float v[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    const float xh = (xx[e] - k.mu[e]) * k.is[e];
+    v[e] = k.gi[e] * (gg[e] - k.k1[e] - xh * k.k2[e]);
+  }
+  return pack8(v);
+}
+
+// Backward reduce: s1 += g' (s1 null: a second BN fed by the same g'), s2 += g' * xhat -- a product and one fused
+// multiply-add, spelled out because whether the compiler fuses the plain expression depends on the code around it
+// (bn_bwd_mask_reduce_kernel, below, is the kernel where it decided otherwise: it keeps its own text).
+__device__ __forceinline__ void bn_reduce8(float* s1, float* s2, const float* gg, const float* xx, const Reg8& mu,
+                                           const Reg8& is) {
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    if (s1) s1[e] += gg[e];
+    s2[e] = __builtin_fmaf(gg[e] * (xx[e] - mu[e]), is[e], s2[e]);
+  }
+}
+
+// The row walk.  Block: 256 threads; a thread owns channel chunk tid % (C/8) -- channels [c0, c0 + 8) -- and walks
+// the rows r0 + k rstep (r0 = tid / (C/8), rstep = 256 / (C/8)) of its block's contiguous row range.
+struct RowWalk {
+  int cv, chunk, r0, rstep, c0;
+  long long rows, rpb;  // the block's range: [blockIdx rpb, + rpb) of the rows
+};
+__device__ __forceinline__ RowWalk row_walk(int C, long long rows, long long rows_per_block) {
+  RowWalk w;
+  w.cv = C / 8;
+  w.chunk = threadIdx.x % w.cv;
+  w.r0 = threadIdx.x / w.cv;
+  w.rstep = 256 / w.cv;
+  w.c0 = w.chunk * 8;
+  w.rows = rows;
+  w.rpb = rows_per_block;
+  return w;
+}
+// load(o) returns the operands of row-vector o (a small struct of u32x4 / a mask byte), use(v, o) consumes them.  The
+// loads of U rows are issued before the first row is consumed (HBM-bound: the bytes in flight per CU set the achieved
+// bandwidth); the rows left over go one at a time.
+template <int U, class Row, class Load, class Use>
+__device__ __forceinline__ void walk_rows(const RowWalk& w, Load load, Use use) {
+  const long long rbeg = blockIdx.x * w.rpb, rend = min(w.rows, rbeg + w.rpb);
+  long long r = rbeg + w.r0;
+  for (; r + (U - 1) * w.rstep < rend; r += U * w.rstep) {
+    const size_t o0 = (size_t)r * w.cv + w.chunk;  // row r + u rstep is 256 u vectors on (rstep cv = 256)
+    Row v[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) load(v[u], o0 + u * 256);
+#pragma unroll
+    for (int u = 0; u < U; ++u) use(v[u], o0 + u * 256);
+  }
+  for (; U > 1 && r < rend; r += w.rstep) {  // (U = 1: the loop above took every row)
+    const size_t o = (size_t)r * w.cv + w.chunk;
+    Row v;
+    load(v, o);
+    use(v, o);
+  }
+}
+
+// After a row of an unrolled iteration: the compiler may not move the next row's unpacking and arithmetic up across
+// this point.  Left to itself it widens all U rows to fp32 at once for the sake of instruction-level parallelism
+// these HBM-bound loops have no use for, and takes 160-240 VGPRs (two or three waves per SIMD) for it.
+__device__ __forceinline__ void row_done() { __builtin_amdgcn_sched_barrier(0); }
+
+// The block epilogue of a reduce: the threads' partials (s1, s2) meet in LDS, are summed over the rstep row groups in
+// row order and go to the block's own slot of acc.  The first block records the slot count.  Every thread of the
+// block calls it.
+__device__ __forceinline__ void block_sums_to_slot(const RowWalk& w, int C, const float* s1, const float* s2,
+                                                   double* acc) {
+  __shared__ float red[2048 * 2];  // [256/(C/8)][C][2] = 4096 floats for any C
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    red[(w.r0 * C + w.c0 + e) * 2] = s1[e];
+    red[(w.r0 * C + w.c0 + e) * 2 + 1] = s2[e];
+  }
+  __syncthreads();
+  bn_write_header(acc, gridDim.x, 0);
+  double* slot = bn_bwd_slots(acc, C) + (size_t)blockIdx.x * C * 2;  // this block's own slot
+  for (int c = threadIdx.x; c < C; c += blockDim.x) {
+    float a = 0.f, b = 0.f;
+    for (int k = 0; k < w.rstep; ++k) {
+      a += red[(k * C + c) * 2];
+      b += red[(k * C + c) * 2 + 1];
+    }
+    slot[2 * c] = (double)a;
+    slot[2 * c + 1] = (double)b;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// out = [relu]( x*scale + shift + [residual*rscale + rshift | residual] ), grid-stride: one thread per vector.
+// The channel block of vector i is i % (C/8); POW2 (C/8 a power of two) takes it as a bit mask.
+// It is the kernel of a C/8 that does not divide 256 (POW2 = false) and of AVT_BN_EW=0; every trunk shape takes the
+// row-walking form below (bn_apply_rw_kernel) -- measured in profiles/bn_rowwalk_kernel_stats_b128.txt.
+template <bool POW2>
+__device__ __forceinline__ int chan_block(long long i, int cv) {
+  return POW2 ? (int)((unsigned)i & (unsigned)(cv - 1)) : (int)(i % cv);
+}
+
 // mk (optional, with relu): the ReLU mask of out as bits, one byte per 8 channels ([rows][C/8] u8):
 // the backward reads 1/16 of the bytes of out for it.
 template <bool POW2>
@@ -148,133 +366,63 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const bf16_t* __restrict_
   const int cv = C / 8;
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < nvec; i += (long long)gridDim.x * blockDim.x) {
     const int c0 = chan_block<POW2>(i, cv) * 8;
-    float f[8];
-    unpack8(reinterpret_cast<const u32x4*>(x)[i], f);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) f[e] = __builtin_fmaf(f[e], scale[c0 + e], shift[c0 + e]);
-    if (res) {
-      float r[8];
-      unpack8(reinterpret_cast<const u32x4*>(res)[i], r);
-      if (rscale) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) f[e] += r[e] * rscale[c0 + e] + rshift[c0 + e];
-      } else {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) f[e] += r[e];
-      }
-    }
-    if (relu) {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) f[e] = fmaxf(f[e], 0.f);
-    }
-    const u32x4 o = pack8(f);
-    reinterpret_cast<u32x4*>(out)[i] = o;
+    const u32x4 xq = ld8(x, i);
+    const u32x4 o = bn_fwd8(xq, res ? ld8(res, i) : xq, res ? (rscale ? 2 : 1) : 0, relu != 0, Mem8::at(scale, c0),
+                            Mem8::at(shift, c0), Mem8::at(rscale, c0), Mem8::at(rshift, c0));
+    st8(out, i, o);
     if (mk) mk[i] = (unsigned char)pos_bits8(o);
   }
 }
 
-// ReLU mask of the backward pass.  Either read from the saved output y (y > 0) or recomputed
-// from the pre-activation: relu(fma(xc, mscale, mshift)) > 0 -- the exact expression bn_apply
-// evaluated in the forward, so the mask is identical without re-reading y.
-__device__ __forceinline__ void relu_mask8(float* gg, const float* xx, const bf16_t* __restrict__ y, size_t off,
-                                           const float* __restrict__ mscale, const float* __restrict__ mshift,
-                                           int c0) {
-  if (y) {
-    float yy[8];
-    unpack8(reinterpret_cast<const u32x4*>(y)[off], yy);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) gg[e] = yy[e] > 0.f ? gg[e] : 0.f;
-  } else if (mscale) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e) gg[e] = __builtin_fmaf(xx[e], mscale[c0 + e], mshift[c0 + e]) > 0.f ? gg[e] : 0.f;
-  }
+// Per-block sums of g' and g'*xhat into slot blockIdx of the workspace, rows dealt by reduce_deal (below).  K: the
+// recomputed mask's (mscale, mshift) in registers or in memory; ROW_DONE: row_done() after each consumed row.
+template <class K, bool ROW_DONE>
+__device__ __forceinline__ void bn_bwd_reduce_block(int form, const bf16_t* __restrict__ g, const bf16_t* __restrict__ y,
+                                                    const float* __restrict__ mscale, const float* __restrict__ mshift,
+                                                    const bf16_t* __restrict__ xc, const float* __restrict__ mean,
+                                                    const float* __restrict__ invstd, double* __restrict__ acc,
+                                                    long long rows, int C, int rows_per_block) {
+  const RowWalk w = row_walk(C, rows, rows_per_block);
+  const Reg8 mu = Reg8::at(mean, w.c0), is = Reg8::at(invstd, w.c0);
+  const K ms = form == kMaskFma ? K::at(mscale, w.c0) : K{}, mh = form == kMaskFma ? K::at(mshift, w.c0) : K{};
+  float s1[8] = {}, s2[8] = {};
+  walk_rows<4, BwdRow>(
+      w, [&](BwdRow& v, size_t o) { load_bwd_row(v, g, xc, form == kMaskY ? y : nullptr, nullptr, nullptr, o); },
+      [&](const BwdRow& v, size_t) {
+        float gg[8], xx[8];
+        unpack8(v.g, gg);
+        unpack8(v.x, xx);
+        relu_mask8(form, gg, xx, v, ms, mh);
+        bn_reduce8(s1, s2, gg, xx, mu, is);
+        if (ROW_DONE) row_done();
+      });
+  block_sums_to_slot(w, C, s1, s2, acc);
 }
 
-// Per-block sums of g' and g'*xhat added into acc[block % SLOTS][C][2].  Block: 256 threads; a
-// thread owns channel chunk (tid % (C/8)) and walks rows tid/(C/8) + k*(256/(C/8)).
+// The A/B partner of bn_bwd_reduce_rw_kernel (AVT_BN_EW bit 16 off): the mask form a run-time branch, the recomputed
+// mask's constants re-read for every row.
 __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const bf16_t* __restrict__ g, const bf16_t* __restrict__ y,
                                                             const float* __restrict__ mscale,
                                                             const float* __restrict__ mshift,
                                                             const bf16_t* __restrict__ xc, const float* __restrict__ mean,
                                                             const float* __restrict__ invstd, double* __restrict__ acc,
                                                             long long rows, int C, int rows_per_block) {
-  __shared__ float red[2048 * 2];  // [256/(C/8)][C][2] = 4096 floats for any C
-  const int cv = C / 8;
-  const int chunk = threadIdx.x % cv, r0 = threadIdx.x / cv, rstep = 256 / cv;
-  const int c0 = chunk * 8;
-  float mu[8], is[8], s1[8], s2[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    mu[e] = mean[c0 + e];
-    is[e] = invstd[c0 + e];
-    s1[e] = 0.f;
-    s2[e] = 0.f;
-  }
-  const long long rbeg = (long long)blockIdx.x * rows_per_block;
-  const long long rend = min(rows, rbeg + rows_per_block);
-  // four rows per iteration: 8-12 independent 16-B loads in flight per thread (HBM-bound: the
-  // bytes in flight per CU set the achieved bandwidth); the remaining rows one at a time
-  long long r = rbeg + r0;
-  constexpr int U = 4;
-  for (; r + (U - 1) * rstep < rend; r += U * rstep) {
-    u32x4 gq[U], xq[U], yq[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const size_t o = (size_t)(r + u * rstep) * cv + chunk;
-      gq[u] = reinterpret_cast<const u32x4*>(g)[o];
-      xq[u] = reinterpret_cast<const u32x4*>(xc)[o];
-      if (y) yq[u] = reinterpret_cast<const u32x4*>(y)[o];
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      float gg[8], xx[8];
-      unpack8(gq[u], gg);
-      unpack8(xq[u], xx);
-      if (y) {
-        float yy[8];
-        unpack8(yq[u], yy);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) gg[e] = yy[e] > 0.f ? gg[e] : 0.f;
-      } else if (mscale) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) gg[e] = __builtin_fmaf(xx[e], mscale[c0 + e], mshift[c0 + e]) > 0.f ? gg[e] : 0.f;
-      }
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        s1[e] += gg[e];
-        s2[e] += gg[e] * (xx[e] - mu[e]) * is[e];
-      }
-    }
-  }
-  for (; r < rend; r += rstep) {
-    const size_t off = (size_t)r * cv + chunk;
-    float gg[8], xx[8];
-    unpack8(reinterpret_cast<const u32x4*>(g)[off], gg);
-    unpack8(reinterpret_cast<const u32x4*>(xc)[off], xx);
-    relu_mask8(gg, xx, y, off, mscale, mshift, c0);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      s1[e] += gg[e];
-      s2[e] += gg[e] * (xx[e] - mu[e]) * is[e];
-    }
-  }
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    red[(r0 * C + c0 + e) * 2] = s1[e];
-    red[(r0 * C + c0 + e) * 2 + 1] = s2[e];
-  }
-  __syncthreads();
-  bn_write_header(acc, gridDim.x, 0);
-  double* slot = bn_bwd_slots(acc, C) + (size_t)blockIdx.x * C * 2;  // this block's own slot
-  for (int c = threadIdx.x; c < C; c += blockDim.x) {
-    float a = 0.f, b = 0.f;
-    for (int k = 0; k < rstep; ++k) {
-      a += red[(k * C + c) * 2];
-      b += red[(k * C + c) * 2 + 1];
-    }
-    slot[2 * c] = (double)a;
-    slot[2 * c + 1] = (double)b;
-  }
+  bn_bwd_reduce_block<Mem8, false>(mask_form(y, mscale), g, y, mscale, mshift, xc, mean, invstd, acc, rows, C,
+                                   rows_per_block);
+}
+
+// The mask form a template parameter (kMaskNone / kMaskY / kMaskFma) and the recomputed mask's (mscale, mshift) in
+// registers.  Rows, slots and the order of every sum are those of bn_bwd_reduce_kernel: the slots hold the same bits.
+template <int MASK>
+__global__ __launch_bounds__(256) void bn_bwd_reduce_rw_kernel(const bf16_t* __restrict__ g, const bf16_t* __restrict__ y,
+                                                               const float* __restrict__ mscale,
+                                                               const float* __restrict__ mshift,
+                                                               const bf16_t* __restrict__ xc,
+                                                               const float* __restrict__ mean,
+                                                               const float* __restrict__ invstd,
+                                                               double* __restrict__ acc, long long rows, int C,
+                                                               int rows_per_block) {
+  bn_bwd_reduce_block<Reg8, true>(MASK, g, y, mscale, mshift, xc, mean, invstd, acc, rows, C, rows_per_block);
 }
 
 // dgamma/dbeta (accumulated into the gradient if non-null) and k1,k2 of channels [c0, c0 + kFinCB) from the
@@ -311,7 +459,8 @@ __global__ __launch_bounds__(kFinThreads) void bn_bwd_finalize2_kernel(double* _
     bn_bwd_finalize_cb(acc2, C, (blockIdx.x - G) * kFinCB, inv_rows, dgamma2, dbeta2, k1b, k2b);
 }
 
-// g_c = gamma*invstd*(g' - k1 - xhat*k2); optionally also writes g' (masked grad) to gmask_out.
+// g_c = gamma*invstd*(g' - k1 - xhat*k2); optionally also writes g' (masked grad) to gmask_out.  Mask: y if given, else
+// (mscale, mshift) if given, else none (mask_form).
 template <bool POW2>
 __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const bf16_t* __restrict__ g, const bf16_t* __restrict__ y,
                                                            const float* __restrict__ mscale,
@@ -324,18 +473,14 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const bf16_t* __restr
   const int cv = C / 8;
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < nvec; i += (long long)gridDim.x * blockDim.x) {
     const int c0 = chan_block<POW2>(i, cv) * 8;
-    float gg[8], xx[8], o[8];
-    unpack8(reinterpret_cast<const u32x4*>(g)[i], gg);
-    unpack8(reinterpret_cast<const u32x4*>(xc)[i], xx);
-    relu_mask8(gg, xx, y, (size_t)i, mscale, mshift, c0);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const int c = c0 + e;
-      const float xh = (xx[e] - mean[c]) * invstd[c];
-      o[e] = gamma[c] * invstd[c] * (gg[e] - k1[c] - xh * k2[c]);
-    }
-    reinterpret_cast<u32x4*>(gc)[i] = pack8(o);
-    if (gmask_out) reinterpret_cast<u32x4*>(gmask_out)[i] = pack8(gg);
+    BwdRow v;
+    load_bwd_row(v, g, xc, y, nullptr, nullptr, i);
+    float gg[8], xx[8];
+    unpack8(v.g, gg);
+    unpack8(v.x, xx);
+    relu_mask8(mask_form(y, mscale), gg, xx, v, Mem8::at(mscale, c0), Mem8::at(mshift, c0));
+    st8(gc, i, bn_bwd8(gg, xx, BwdK<Mem8>::at(mean, invstd, gamma, k1, k2, c0)));
+    if (gmask_out) st8(gmask_out, i, pack8(gg));
   }
 }
 
@@ -358,6 +503,11 @@ struct MaskBwdArgs {
   int C, rows_per_block;
 };
 
+// This kernel keeps its own walk, body and three-sum epilogue.  The compiler fuses its plain `s += g' * (xc - mean) *
+// invstd` into a multiply-add for some elements and not for others (none in <false>, the odd ones in <true>), and the
+// slots -- with k1 / k2 / dgamma / gc behind them -- hold exactly those roundings.  On walk_rows the plain expression
+// fuses differently (other bits); with the rounding spelled out per element the bits hold but <false> measured 5 %
+// slower (profiles/bn_one_walker.txt, section 2).  So the text the compiler made its choice for stays as it was.
 __device__ __forceinline__ void mask8(float* gg, unsigned bits) {
 #pragma unroll
   for (int e = 0; e < 8; ++e) gg[e] = (bits >> e) & 1u ? gg[e] : 0.f;
@@ -464,36 +614,32 @@ struct MaskApplyArgs {
   int C;
 };
 
+// row-vector o of a mask apply: k1 / k2 the constants of the first / second BN (k2 unused without TWO)
+template <bool TWO, class K>
+__device__ __forceinline__ void bn_bwd_mask_apply8(const MaskApplyArgs& a, const BwdRow& v, size_t o, const BwdK<K>& k1,
+                                                   const BwdK<K>& k2) {
+  float gg[8], xx[8];
+  unpack8(v.g, gg);
+  unpack8(v.x, xx);
+  relu_mask8(kMaskBits, gg, xx, v);
+  st8(a.gc, o, bn_bwd8(gg, xx, k1));
+  if (TWO) {
+    unpack8(v.x2, xx);
+    st8(a.gc2, o, bn_bwd8(gg, xx, k2));
+  }
+}
+
 template <bool TWO>
 __global__ __launch_bounds__(256) void bn_bwd_mask_apply_kernel(MaskApplyArgs a) {
   const int cv = a.C / 8;  // a power of two dividing 256 (checked by the host)
   for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < a.nvec;
        i += (long long)gridDim.x * blockDim.x) {
-    const int c0 = (int)((unsigned)i & (unsigned)(cv - 1)) * 8;
-    float gg[8], xx[8], o[8];
-    unpack8(reinterpret_cast<const u32x4*>(a.g)[i], gg);
-    unpack8(reinterpret_cast<const u32x4*>(a.xc)[i], xx);
-    const unsigned bits = a.mk[i];
-    u32x4 x2q;
-    if (TWO) x2q = reinterpret_cast<const u32x4*>(a.xc2)[i];
-    mask8(gg, bits);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const int c = c0 + e;
-      const float xh = (xx[e] - a.mean[c]) * a.invstd[c];
-      o[e] = a.gamma[c] * a.invstd[c] * (gg[e] - a.k1[c] - xh * a.k2[c]);
-    }
-    reinterpret_cast<u32x4*>(a.gc)[i] = pack8(o);
-    if (TWO) {
-      unpack8(x2q, xx);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const int c = c0 + e;
-        const float xh = (xx[e] - a.mean2[c]) * a.invstd2[c];
-        o[e] = a.gamma2[c] * a.invstd2[c] * (gg[e] - a.k1b[c] - xh * a.k2b[c]);
-      }
-      reinterpret_cast<u32x4*>(a.gc2)[i] = pack8(o);
-    }
+    const int c0 = chan_block<true>(i, cv) * 8;
+    BwdRow v;
+    load_bwd_row(v, a.g, a.xc, nullptr, a.mk, TWO ? a.xc2 : nullptr, i);
+    bn_bwd_mask_apply8<TWO>(a, v, i,
+                            BwdK<Mem8>::at(a.mean, a.invstd, a.gamma, a.k1, a.k2, c0),
+                            BwdK<Mem8>::at(a.mean2, a.invstd2, a.gamma2, a.k1b, a.k2b, c0));
   }
 }
 
@@ -505,12 +651,9 @@ static int ew_grid(long long nvec) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// Row-walking forms of the elementwise passes (C/8 dividing 256: every trunk shape).  As in bn_bwd_reduce_kernel a
-// thread owns channel chunk tid % (C/8) and walks the rows r0 + k rstep (r0 = tid / (C/8), rstep = 256 / (C/8)) of
-// its block's contiguous row range [blockIdx rpb, +rpb): its 8-channel constants are loaded ONCE, into registers,
-// and the data loads of U rows are issued before the first is consumed; the rows left over go one at a time.  The
-// optional operands are template parameters (no uniform branches in the loop).  Per element the arithmetic is the
-// expression of the grid-stride kernels above in the same order (gamma*invstd is the same product, taken once), so
+// Row-walking forms of the elementwise passes (C/8 dividing 256: every trunk shape): walk_rows over the block's row
+// range, the thread's 8-channel constants in registers (Reg8).  The optional operands are template parameters (no
+// uniform branches in the loop).  Per element the arithmetic is the formula the grid-stride kernels above call, so
 // every output bit is the same.
 //
 // AVT_BN_EW (read once; a performance knob, the results are the same bits): 0 = the grid-stride kernels above and
@@ -536,6 +679,14 @@ struct RowDeal {
   int nblk;
   long long rpb;
 };
+// rows dealt to about `target` blocks: whole rstep steps, at least U of them
+static RowDeal deal_rows(long long rows, int C, int target, int U) {
+  const int rstep = 256 / (C / 8);
+  long long rpb = (rows + target - 1) / target;
+  rpb = ((rpb + rstep - 1) / rstep) * rstep;
+  if (rpb < (long long)U * rstep) rpb = (long long)U * rstep;
+  return {(int)((rows + rpb - 1) / rpb), rpb};
+}
 static RowDeal rw_deal(long long rows, int C, int U) {
   static int target = 0;  // blocks per launch: queried once
   if (target == 0) {
@@ -550,23 +701,10 @@ static RowDeal rw_deal(long long rows, int C, int U) {
     if (bpc > 64) bpc = 64;
     target = cus * bpc;
   }
-  const int rstep = 256 / (C / 8);
-  long long rpb = (rows + target - 1) / target;
-  rpb = ((rpb + rstep - 1) / rstep) * rstep;
-  if (rpb < (long long)U * rstep) rpb = (long long)U * rstep;
-  return {(int)((rows + rpb - 1) / rpb), rpb};
+  return deal_rows(rows, C, target, U);
 }
-
-// After a row of an unrolled iteration: the compiler may not move the next row's unpacking and arithmetic up across
-// this point.  Left to itself it widens all U rows to fp32 at once for the sake of instruction-level parallelism
-// these HBM-bound loops have no use for, and takes 160-240 VGPRs (two or three waves per SIMD) for it.
-__device__ __forceinline__ void row_done() { __builtin_amdgcn_sched_barrier(0); }
-
-// the 8 channel constants of a thread's chunk
-__device__ __forceinline__ void load8(float* d, const float* __restrict__ s, int c0) {
-#pragma unroll
-  for (int e = 0; e < 8; ++e) d[e] = s[c0 + e];
-}
+// The reduces' deal (train and eval): ~2 blocks per CU of rows -- one slot per block, and the finalize sums the slots.
+static RowDeal reduce_deal(long long rows, int C) { return deal_rows(rows, C, 512, 1); }
 
 // RES: 0 no residual, 1 + residual, 2 + residual*rscale + rshift.  MK: the ReLU mask bits (with RELU).
 template <int RES, bool RELU, bool MK, int U>
@@ -577,59 +715,34 @@ __global__ __launch_bounds__(256) void bn_apply_rw_kernel(const bf16_t* __restri
                                                           const float* __restrict__ rshift, bf16_t* __restrict__ out,
                                                           unsigned char* __restrict__ mk, long long rows, int C,
                                                           long long rpb) {
-  const int cv = C / 8;
-  const int chunk = threadIdx.x % cv, r0 = threadIdx.x / cv, rstep = 256 / cv;
-  const int c0 = chunk * 8;
-  float sc[8], sh[8], rs[8], rh[8];
-  load8(sc, scale, c0);
-  load8(sh, shift, c0);
-  if (RES == 2) {
-    load8(rs, rscale, c0);
-    load8(rh, rshift, c0);
-  }
-  const long long rbeg = blockIdx.x * rpb, rend = min(rows, rbeg + rpb);
+  const RowWalk w = row_walk(C, rows, rpb);
+  const Reg8 sc = Reg8::at(scale, w.c0), sh = Reg8::at(shift, w.c0);
+  const Reg8 rs = RES == 2 ? Reg8::at(rscale, w.c0) : Reg8{}, rh = RES == 2 ? Reg8::at(rshift, w.c0) : Reg8{};
   auto one = [&](const u32x4& xq, const u32x4& rq, size_t o) {
-    float f[8];
-    unpack8(xq, f);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) f[e] = __builtin_fmaf(f[e], sc[e], sh[e]);
-    if (RES) {
-      float r[8];
-      unpack8(rq, r);
-      if (RES == 2) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) f[e] += r[e] * rs[e] + rh[e];
-      } else {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) f[e] += r[e];
-      }
-    }
-    if (RELU) {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) f[e] = fmaxf(f[e], 0.f);
-    }
-    const u32x4 v = pack8(f);
-    reinterpret_cast<u32x4*>(out)[o] = v;
-    if (MK) mk[o] = (unsigned char)pos_bits8(v);
+    const u32x4 q = bn_fwd8(xq, rq, RES, RELU, sc, sh, rs, rh);
+    st8(out, o, q);
+    if (MK) mk[o] = (unsigned char)pos_bits8(q);
     row_done();
   };
-  long long r = rbeg + r0;
-  for (; r + (U - 1) * rstep < rend; r += U * rstep) {
-    const size_t o0 = (size_t)r * cv + chunk;  // row r + u rstep is 256 u vectors on (rstep cv = 256)
+  // walk_rows' loop written out, with x and the residual in two arrays: as one struct per row behind the walker's
+  // callables the <1, relu, mask> and <2, relu, *> forms took 1-4 VGPRs more (79 -> 81: a wave per SIMD)
+  const long long rbeg = blockIdx.x * rpb, rend = min(rows, rbeg + rpb);
+  long long r = rbeg + w.r0;
+  for (; r + (U - 1) * w.rstep < rend; r += U * w.rstep) {
+    const size_t o0 = (size_t)r * w.cv + w.chunk;  // row r + u rstep is 256 u vectors on (rstep cv = 256)
     u32x4 xq[U], rq[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
-      const size_t o = o0 + u * 256;
-      xq[u] = reinterpret_cast<const u32x4*>(x)[o];
-      if (RES) rq[u] = reinterpret_cast<const u32x4*>(res)[o];
+      xq[u] = ld8(x, o0 + u * 256);
+      if (RES) rq[u] = ld8(res, o0 + u * 256);
     }
 #pragma unroll
     for (int u = 0; u < U; ++u) one(xq[u], RES ? rq[u] : xq[u], o0 + u * 256);
   }
-  for (; r < rend; r += rstep) {
-    const size_t o = (size_t)r * cv + chunk;
-    const u32x4 xq = reinterpret_cast<const u32x4*>(x)[o];
-    one(xq, RES ? reinterpret_cast<const u32x4*>(res)[o] : xq, o);
+  for (; r < rend; r += w.rstep) {
+    const size_t o = (size_t)r * w.cv + w.chunk;
+    const u32x4 xq = ld8(x, o);
+    one(xq, RES ? ld8(res, o) : xq, o);
   }
 }
 
@@ -664,7 +777,17 @@ static void bn_apply_rw_dispatch(const bf16_t* x, const float* scale, const floa
 #undef AVT_FWD_RW
 }
 
-// MASK: 0 none (g is g'), 1 y > 0, 2 fma(xc, mscale, mshift) > 0.  GM: also writes g' to gmask_out.
+// The launchers' one mask-form dispatch: f(std::integral_constant<int, form>) of mask_form(y, mscale).
+template <class F>
+static void with_mask_form(const void* y, const float* mscale, F f) {
+  switch (mask_form(y, mscale)) {
+    case kMaskY: return f(std::integral_constant<int, kMaskY>{});
+    case kMaskFma: return f(std::integral_constant<int, kMaskFma>{});
+    default: return f(std::integral_constant<int, kMaskNone>{});
+  }
+}
+
+// MASK: kMaskNone (g is g'), kMaskY, kMaskFma.  GM: also writes g' to gmask_out.
 template <int MASK, bool GM, int U>
 __global__ __launch_bounds__(256) void bn_bwd_apply_rw_kernel(
     const bf16_t* __restrict__ g, const bf16_t* __restrict__ y, const float* __restrict__ mscale,
@@ -672,152 +795,53 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_rw_kernel(
     const float* __restrict__ invstd, const float* __restrict__ gamma, const float* __restrict__ k1,
     const float* __restrict__ k2, bf16_t* __restrict__ gc, bf16_t* __restrict__ gmask_out, long long rows, int C,
     long long rpb) {
-  const int cv = C / 8;
-  const int chunk = threadIdx.x % cv, r0 = threadIdx.x / cv, rstep = 256 / cv;
-  const int c0 = chunk * 8;
-  float mu[8], is[8], gi[8], a1[8], a2[8], ms[8], mh[8];
-  load8(mu, mean, c0);
-  load8(is, invstd, c0);
-  load8(gi, gamma, c0);
-  load8(a1, k1, c0);
-  load8(a2, k2, c0);
-#pragma unroll
-  for (int e = 0; e < 8; ++e) gi[e] = gi[e] * is[e];
-  if (MASK == 2) {
-    load8(ms, mscale, c0);
-    load8(mh, mshift, c0);
-  }
-  const long long rbeg = blockIdx.x * rpb, rend = min(rows, rbeg + rpb);
-  auto one = [&](const u32x4& gq, const u32x4& xq, const u32x4& yq, size_t o) {
-    float gg[8], xx[8], v[8];
-    unpack8(gq, gg);
-    unpack8(xq, xx);
-    if (MASK == 1) {
-      float yy[8];
-      unpack8(yq, yy);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) gg[e] = yy[e] > 0.f ? gg[e] : 0.f;
-    } else if (MASK == 2) {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) gg[e] = __builtin_fmaf(xx[e], ms[e], mh[e]) > 0.f ? gg[e] : 0.f;
-    }
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const float xh = (xx[e] - mu[e]) * is[e];
-      v[e] = gi[e] * (gg[e] - a1[e] - xh * a2[e]);
-    }
-    reinterpret_cast<u32x4*>(gc)[o] = pack8(v);
-    if (GM) reinterpret_cast<u32x4*>(gmask_out)[o] = pack8(gg);
-    row_done();
-  };
-  long long r = rbeg + r0;
-  for (; r + (U - 1) * rstep < rend; r += U * rstep) {
-    const size_t o0 = (size_t)r * cv + chunk;  // row r + u rstep is 256 u vectors on (rstep cv = 256)
-    u32x4 gq[U], xq[U], yq[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const size_t o = o0 + u * 256;
-      gq[u] = reinterpret_cast<const u32x4*>(g)[o];
-      xq[u] = reinterpret_cast<const u32x4*>(xc)[o];
-      if (MASK == 1) yq[u] = reinterpret_cast<const u32x4*>(y)[o];
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) one(gq[u], xq[u], MASK == 1 ? yq[u] : xq[u], o0 + u * 256);
-  }
-  for (; r < rend; r += rstep) {
-    const size_t o = (size_t)r * cv + chunk;
-    const u32x4 xq = reinterpret_cast<const u32x4*>(xc)[o];
-    one(reinterpret_cast<const u32x4*>(g)[o], xq, MASK == 1 ? reinterpret_cast<const u32x4*>(y)[o] : xq, o);
-  }
+  const RowWalk w = row_walk(C, rows, rpb);
+  const BwdK<Reg8> k = BwdK<Reg8>::at(mean, invstd, gamma, k1, k2, w.c0);
+  const Reg8 ms = MASK == kMaskFma ? Reg8::at(mscale, w.c0) : Reg8{}, mh = MASK == kMaskFma ? Reg8::at(mshift, w.c0) : Reg8{};
+  walk_rows<U, BwdRow>(
+      w, [&](BwdRow& v, size_t o) { load_bwd_row(v, g, xc, MASK == kMaskY ? y : nullptr, nullptr, nullptr, o); },
+      [&](const BwdRow& v, size_t o) {
+        float gg[8], xx[8];
+        unpack8(v.g, gg);
+        unpack8(v.x, xx);
+        relu_mask8(MASK, gg, xx, v, ms, mh);
+        st8(gc, o, bn_bwd8(gg, xx, k));
+        if (GM) st8(gmask_out, o, pack8(gg));
+        row_done();
+      });
 }
 
-// the form of bn_bwd_apply_kernel<true>'s arguments (y, then mscale, decide the mask as in relu_mask8)
+// the form of bn_bwd_apply_kernel<true>'s arguments; avt_bn_relu_bwd (kMaskFma) has no gmask_out
 static void bn_bwd_apply_rw_launch(const bf16_t* g, const bf16_t* y, const float* mscale, const float* mshift,
                                    const bf16_t* xc, const float* mean, const float* invstd, const float* gamma,
                                    const float* k1, const float* k2, bf16_t* gc, bf16_t* gmask_out, long long rows,
                                    int C, hipStream_t st) {
   constexpr int U = 4;
   const RowDeal d = rw_deal(rows, C, U);
-#define AVT_BWD_RW(MASK, GM)                                                                                        \
-  hipLaunchKernelGGL((bn_bwd_apply_rw_kernel<MASK, GM, U>), dim3(d.nblk), dim3(256), 0, st, g, y, mscale, mshift, xc, \
-                     mean, invstd, gamma, k1, k2, gc, gmask_out, rows, C, d.rpb)
-  if (y) {
-    if (gmask_out) AVT_BWD_RW(1, true); else AVT_BWD_RW(1, false);
-  } else if (mscale) {
-    AVT_BWD_RW(2, false);  // (avt_bn_relu_bwd: no gmask_out)
-  } else {
-    if (gmask_out) AVT_BWD_RW(0, true); else AVT_BWD_RW(0, false);
-  }
-#undef AVT_BWD_RW
+  with_mask_form(y, mscale, [&](auto m) {
+    constexpr int MASK = decltype(m)::value;
+    auto launch = [&](auto gm) {
+      hipLaunchKernelGGL((bn_bwd_apply_rw_kernel<MASK, decltype(gm)::value, U>), dim3(d.nblk), dim3(256), 0, st, g, y,
+                         mscale, mshift, xc, mean, invstd, gamma, k1, k2, gc, gmask_out, rows, C, d.rpb);
+    };
+    if constexpr (MASK != kMaskFma)
+      if (gmask_out) return launch(std::true_type{});
+    launch(std::false_type{});
+  });
 }
 
 // bn_bwd_mask_apply_kernel's row-walking form (MaskApplyArgs::nvec = rows * C/8)
 template <bool TWO, int U>
 __global__ __launch_bounds__(256) void bn_bwd_mask_apply_rw_kernel(MaskApplyArgs a, long long rows, long long rpb) {
-  const int cv = a.C / 8;
-  const int chunk = threadIdx.x % cv, r0 = threadIdx.x / cv, rstep = 256 / cv;
-  const int c0 = chunk * 8;
-  float mu[8], is[8], gi[8], a1[8], a2[8], mu2[8], is2[8], gi2[8], b1[8], b2[8];
-  load8(mu, a.mean, c0);
-  load8(is, a.invstd, c0);
-  load8(gi, a.gamma, c0);
-  load8(a1, a.k1, c0);
-  load8(a2, a.k2, c0);
-#pragma unroll
-  for (int e = 0; e < 8; ++e) gi[e] = gi[e] * is[e];
-  if (TWO) {
-    load8(mu2, a.mean2, c0);
-    load8(is2, a.invstd2, c0);
-    load8(gi2, a.gamma2, c0);
-    load8(b1, a.k1b, c0);
-    load8(b2, a.k2b, c0);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) gi2[e] = gi2[e] * is2[e];
-  }
-  const long long rbeg = blockIdx.x * rpb, rend = min(rows, rbeg + rpb);
-  auto one = [&](const u32x4& gq, unsigned bits, const u32x4& xq, const u32x4& x2q, size_t o) {
-    float gg[8], xx[8], v[8];
-    unpack8(gq, gg);
-    unpack8(xq, xx);
-    mask8(gg, bits);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const float xh = (xx[e] - mu[e]) * is[e];
-      v[e] = gi[e] * (gg[e] - a1[e] - xh * a2[e]);
-    }
-    reinterpret_cast<u32x4*>(a.gc)[o] = pack8(v);
-    if (TWO) {
-      unpack8(x2q, xx);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const float xh = (xx[e] - mu2[e]) * is2[e];
-        v[e] = gi2[e] * (gg[e] - b1[e] - xh * b2[e]);
-      }
-      reinterpret_cast<u32x4*>(a.gc2)[o] = pack8(v);
-    }
-    row_done();
-  };
-  long long r = rbeg + r0;
-  for (; r + (U - 1) * rstep < rend; r += U * rstep) {
-    const size_t o0 = (size_t)r * cv + chunk;  // row r + u rstep is 256 u vectors on (rstep cv = 256)
-    u32x4 gq[U], xq[U], x2q[U];
-    unsigned bq[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const size_t o = o0 + u * 256;
-      gq[u] = reinterpret_cast<const u32x4*>(a.g)[o];
-      xq[u] = reinterpret_cast<const u32x4*>(a.xc)[o];
-      if (TWO) x2q[u] = reinterpret_cast<const u32x4*>(a.xc2)[o];
-      bq[u] = a.mk[o];
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) one(gq[u], bq[u], xq[u], TWO ? x2q[u] : xq[u], o0 + u * 256);
-  }
-  for (; r < rend; r += rstep) {
-    const size_t o = (size_t)r * cv + chunk;
-    const u32x4 xq = reinterpret_cast<const u32x4*>(a.xc)[o];
-    one(reinterpret_cast<const u32x4*>(a.g)[o], a.mk[o], xq, TWO ? reinterpret_cast<const u32x4*>(a.xc2)[o] : xq, o);
-  }
+  const RowWalk w = row_walk(a.C, rows, rpb);
+  const BwdK<Reg8> k1 = BwdK<Reg8>::at(a.mean, a.invstd, a.gamma, a.k1, a.k2, w.c0);
+  const BwdK<Reg8> k2 = TWO ? BwdK<Reg8>::at(a.mean2, a.invstd2, a.gamma2, a.k1b, a.k2b, w.c0) : BwdK<Reg8>{};
+  walk_rows<U, BwdRow>(
+      w, [&](BwdRow& v, size_t o) { load_bwd_row(v, a.g, a.xc, nullptr, a.mk, TWO ? a.xc2 : nullptr, o); },
+      [&](const BwdRow& v, size_t o) {
+        bn_bwd_mask_apply8<TWO>(a, v, o, k1, k2);
+        row_done();
+      });
 }
 
 template <bool TWO>
@@ -825,94 +849,6 @@ static void bn_bwd_mask_apply_rw_launch(const MaskApplyArgs& p, long long rows, 
   constexpr int U = TWO ? 2 : 4;  // (TWO holds 80 constants: two rows in flight keep it at four waves per SIMD)
   const RowDeal d = rw_deal(rows, p.C, U);
   hipLaunchKernelGGL((bn_bwd_mask_apply_rw_kernel<TWO, U>), dim3(d.nblk), dim3(256), 0, st, p, rows, d.rpb);
-}
-
-// bn_bwd_reduce_kernel with the mask form a template parameter (MASK as bn_bwd_apply_rw_kernel) and the recomputed
-// mask's (mscale, mshift) in registers, not re-read for every row.  Rows, slots and the order of every sum are
-// those of bn_bwd_reduce_kernel: the slots hold the same bits.
-template <int MASK>
-__global__ __launch_bounds__(256) void bn_bwd_reduce_rw_kernel(const bf16_t* __restrict__ g, const bf16_t* __restrict__ y,
-                                                               const float* __restrict__ mscale,
-                                                               const float* __restrict__ mshift,
-                                                               const bf16_t* __restrict__ xc,
-                                                               const float* __restrict__ mean,
-                                                               const float* __restrict__ invstd,
-                                                               double* __restrict__ acc, long long rows, int C,
-                                                               int rows_per_block) {
-  __shared__ float red[2048 * 2];  // [256/(C/8)][C][2] = 4096 floats for any C
-  const int cv = C / 8;
-  const int chunk = threadIdx.x % cv, r0 = threadIdx.x / cv, rstep = 256 / cv;
-  const int c0 = chunk * 8;
-  float mu[8], is[8], ms[8], mh[8], s1[8], s2[8];
-  load8(mu, mean, c0);
-  load8(is, invstd, c0);
-  if (MASK == 2) {
-    load8(ms, mscale, c0);
-    load8(mh, mshift, c0);
-  }
-#pragma unroll
-  for (int e = 0; e < 8; ++e) s1[e] = s2[e] = 0.f;
-  const long long rbeg = (long long)blockIdx.x * rows_per_block;
-  const long long rend = min(rows, rbeg + rows_per_block);
-  auto one = [&](const u32x4& gq, const u32x4& xq, const u32x4& yq) {
-    float gg[8], xx[8];
-    unpack8(gq, gg);
-    unpack8(xq, xx);
-    if (MASK == 1) {
-      float yy[8];
-      unpack8(yq, yy);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) gg[e] = yy[e] > 0.f ? gg[e] : 0.f;
-    } else if (MASK == 2) {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) gg[e] = __builtin_fmaf(xx[e], ms[e], mh[e]) > 0.f ? gg[e] : 0.f;
-    }
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      s1[e] += gg[e];
-      // bn_bwd_reduce_kernel's `s2 += g' (x - mu) is` compiles to a product and one fused multiply-add; written
-      // out, because whether the compiler fuses the plain expression depends on the code around it
-      s2[e] = __builtin_fmaf(gg[e] * (xx[e] - mu[e]), is[e], s2[e]);
-    }
-    row_done();
-  };
-  long long r = rbeg + r0;
-  constexpr int U = 4;
-  for (; r + (U - 1) * rstep < rend; r += U * rstep) {
-    const size_t o0 = (size_t)r * cv + chunk;  // row r + u rstep is 256 u vectors on (rstep cv = 256)
-    u32x4 gq[U], xq[U], yq[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const size_t o = o0 + u * 256;
-      gq[u] = reinterpret_cast<const u32x4*>(g)[o];
-      xq[u] = reinterpret_cast<const u32x4*>(xc)[o];
-      if (MASK == 1) yq[u] = reinterpret_cast<const u32x4*>(y)[o];
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) one(gq[u], xq[u], MASK == 1 ? yq[u] : xq[u]);
-  }
-  for (; r < rend; r += rstep) {
-    const size_t o = (size_t)r * cv + chunk;
-    const u32x4 xq = reinterpret_cast<const u32x4*>(xc)[o];
-    one(reinterpret_cast<const u32x4*>(g)[o], xq, MASK == 1 ? reinterpret_cast<const u32x4*>(y)[o] : xq);
-  }
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    red[(r0 * C + c0 + e) * 2] = s1[e];
-    red[(r0 * C + c0 + e) * 2 + 1] = s2[e];
-  }
-  __syncthreads();
-  bn_write_header(acc, gridDim.x, 0);
-  double* slot = bn_bwd_slots(acc, C) + (size_t)blockIdx.x * C * 2;  // this block's own slot
-  for (int c = threadIdx.x; c < C; c += blockDim.x) {
-    float a = 0.f, b = 0.f;
-    for (int k = 0; k < rstep; ++k) {
-      a += red[(k * C + c) * 2];
-      b += red[(k * C + c) * 2 + 1];
-    }
-    slot[2 * c] = (double)a;
-    slot[2 * c + 1] = (double)b;
-  }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1130,24 +1066,37 @@ __global__ __launch_bounds__(kStemBwdThreads) void stem_maxpool_bn_bwd_apply_ker
 static void bn_bwd_reduce_launch(const bf16_t* g, const bf16_t* y, const float* mscale, const float* mshift,
                                  const bf16_t* xc, const float* mean, const float* invstd, double* acc, long long rows,
                                  int C, hipStream_t st) {
-  // ~2 blocks per CU of rows (more blocks measured slower: their fp64 atomics contend)
-  long long rpb = (rows + 511) / 512;
-  const int rstep = 256 / (C / 8);
-  rpb = ((rpb + rstep - 1) / rstep) * rstep;
-  if (rpb < rstep) rpb = rstep;
-  const int nblk = (int)((rows + rpb - 1) / rpb);
+  const RowDeal d = reduce_deal(rows, C);
   if (!bn_ew(kEwReduce))
-    hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3(nblk), dim3(256), 0, st, g, y, mscale, mshift, xc, mean, invstd, acc,
-                       rows, C, (int)rpb);
-  else if (y)
-    hipLaunchKernelGGL(bn_bwd_reduce_rw_kernel<1>, dim3(nblk), dim3(256), 0, st, g, y, mscale, mshift, xc, mean, invstd,
-                       acc, rows, C, (int)rpb);
-  else if (mscale)
-    hipLaunchKernelGGL(bn_bwd_reduce_rw_kernel<2>, dim3(nblk), dim3(256), 0, st, g, y, mscale, mshift, xc, mean, invstd,
-                       acc, rows, C, (int)rpb);
+    hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3(d.nblk), dim3(256), 0, st, g, y, mscale, mshift, xc, mean, invstd,
+                       acc, rows, C, (int)d.rpb);
   else
-    hipLaunchKernelGGL(bn_bwd_reduce_rw_kernel<0>, dim3(nblk), dim3(256), 0, st, g, y, mscale, mshift, xc, mean, invstd,
-                       acc, rows, C, (int)rpb);
+    with_mask_form(y, mscale, [&](auto m) {
+      hipLaunchKernelGGL(bn_bwd_reduce_rw_kernel<decltype(m)::value>, dim3(d.nblk), dim3(256), 0, st, g, y, mscale,
+                         mshift, xc, mean, invstd, acc, rows, C, (int)d.rpb);
+    });
+}
+
+// k1 / k2 of a backward workspace: 2C floats behind the header (avt_common.h)
+static float* bn_k1(double* acc) { return (float*)(acc + kBnHdr); }
+
+// The finalize of one backward workspace, or of two in one launch (acc2: a first block's second BN): dgamma / dbeta
+// are added into the gradients, k1 / k2 left in the workspace.  diag: under AVT_DIAG_SKIP bit 64 it is launched once
+// more, under bit 2 not at all (timing only).
+static void bn_bwd_finalize_launch(hipStream_t st, int C, double inv_rows, bool diag, double* acc, float* dgamma,
+                                   float* dbeta, double* acc2 = nullptr, float* dgamma2 = nullptr,
+                                   float* dbeta2 = nullptr) {
+  const int G = (C + kFinCB - 1) / kFinCB;
+  auto launch = [&] {
+    if (acc2)
+      hipLaunchKernelGGL(bn_bwd_finalize2_kernel, dim3(2 * G), dim3(kFinThreads), 0, st, acc, acc2, C, inv_rows, dgamma,
+                         dbeta, bn_k1(acc), bn_k1(acc) + C, dgamma2, dbeta2, bn_k1(acc2), bn_k1(acc2) + C);
+    else
+      hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(G), dim3(kFinThreads), 0, st, acc, C, inv_rows, dgamma, dbeta,
+                         bn_k1(acc), bn_k1(acc) + C);
+  };
+  if (diag && diag_skip(64, st)) launch();
+  if (!diag || !diag_skip(2, st)) launch();
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1155,7 +1104,7 @@ static void bn_bwd_reduce_launch(const bf16_t* g, const bf16_t* y, const float* 
 // mean terms of the train-mode rule vanish and one pass does everything: g' = g * mask, gc = gamma*invstd*g' (and
 // gc2 of a second BN fed by the same g': a first block's bn2 + downsample.1), and -- only for a BN whose dgamma or
 // dbeta is wanted -- the block's (sum g', sum g'*xhat) into its own slot of the fixed-order workspace, xhat =
-// (xc - running_mean)*invstd.  Rows are dealt to blocks and threads as in bn_bwd_reduce_kernel.
+// (xc - running_mean)*invstd.  Rows are dealt to blocks and threads as in the train-mode reduces (one row at a time).
 struct EvalBwdArgs {
   const bf16_t* g;
   const bf16_t* y;      // mask y > 0, or
@@ -1175,73 +1124,47 @@ struct EvalBwdArgs {
 
 template <bool TWO, bool BITS>
 __global__ __launch_bounds__(256) void bn_eval_bwd_kernel(EvalBwdArgs a) {
-  __shared__ float red[2048 * 2];
   constexpr int NB = TWO ? 2 : 1;
-  const int C = a.C, cv = C / 8;
-  const int chunk = threadIdx.x % cv, r0 = threadIdx.x / cv, rstep = 256 / cv;
-  const int c0 = chunk * 8;
-  float mu[NB][8], is[NB][8], gi[NB][8], s1[8], s2[NB][8];
+  const RowWalk w = row_walk(a.C, a.rows, a.rows_per_block);
+  const int form = BITS ? kMaskBits : mask_form(a.y, a.mscale);
+  Reg8 mu[NB], is[NB], gi[NB];
+  float s1[8] = {}, s2[NB][8] = {};
 #pragma unroll
-  for (int b = 0; b < NB; ++b)
+  for (int b = 0; b < NB; ++b) {
+    mu[b] = Reg8::at(a.mean[b], w.c0);
+    is[b] = Reg8::at(a.invstd[b], w.c0);
+    gi[b] = Reg8::at(a.gamma[b], w.c0);
 #pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      mu[b][e] = a.mean[b][c0 + e];
-      is[b][e] = a.invstd[b][c0 + e];
-      gi[b][e] = a.gamma[b][c0 + e] * is[b][e];
-      s2[b][e] = 0.f;
-    }
-#pragma unroll
-  for (int e = 0; e < 8; ++e) s1[e] = 0.f;
-  const long long rbeg = (long long)blockIdx.x * a.rows_per_block;
-  const long long rend = min(a.rows, rbeg + a.rows_per_block);
-  for (long long r = rbeg + r0; r < rend; r += rstep) {
-    const size_t off = (size_t)r * cv + chunk;
-    float gg[8], xx[8], o[8];
-    unpack8(reinterpret_cast<const u32x4*>(a.g)[off], gg);
-    unpack8(reinterpret_cast<const u32x4*>(a.xc[0])[off], xx);
-    if (BITS)
-      mask8(gg, a.mk[off]);
-    else
-      relu_mask8(gg, xx, a.y, off, a.mscale, a.mshift, c0);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      s1[e] += gg[e];
-      s2[0][e] += gg[e] * (xx[e] - mu[0][e]) * is[0][e];
-      o[e] = gi[0][e] * gg[e];
-    }
-    reinterpret_cast<u32x4*>(a.gc[0])[off] = pack8(o);
-    if (a.gmask_out) reinterpret_cast<u32x4*>(a.gmask_out)[off] = pack8(gg);
-    if (TWO) {
-      unpack8(reinterpret_cast<const u32x4*>(a.xc[NB - 1])[off], xx);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        s2[NB - 1][e] += gg[e] * (xx[e] - mu[NB - 1][e]) * is[NB - 1][e];
-        o[e] = gi[NB - 1][e] * gg[e];
-      }
-      reinterpret_cast<u32x4*>(a.gc[NB - 1])[off] = pack8(o);
-    }
+    for (int e = 0; e < 8; ++e) gi[b].v[e] *= is[b][e];
   }
+  // target b of row-vector o: its share of the sums, and gc = gamma*invstd*g'
+  auto target = [&](int b, const float* gg, const float* xx, size_t o) {
+    float v[8];
+    bn_reduce8(b ? nullptr : s1, s2[b], gg, xx, mu[b], is[b]);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v[e] = gi[b][e] * gg[e];
+    st8(a.gc[b], o, pack8(v));
+  };
+  walk_rows<1, BwdRow>(
+      w,
+      [&](BwdRow& v, size_t o) { load_bwd_row(v, a.g, a.xc[0], form == kMaskY ? a.y : nullptr, BITS ? a.mk : nullptr, nullptr, o); },
+      [&](const BwdRow& v, size_t o) {
+        float gg[8], xx[8];
+        unpack8(v.g, gg);
+        unpack8(v.x, xx);
+        relu_mask8(form, gg, xx, v, Mem8::at(a.mscale, w.c0), Mem8::at(a.mshift, w.c0));
+        target(0, gg, xx, o);
+        if (a.gmask_out) st8(a.gmask_out, o, pack8(gg));
+        if (TWO) {
+          unpack8(ld8(a.xc[NB - 1], o), xx);  // (read here, after the first BN's store: one row's operands at a time)
+          target(NB - 1, gg, xx, o);
+        }
+      });
 #pragma unroll
   for (int b = 0; b < NB; ++b) {
     if (!a.acc[b]) continue;  // (uniform over the block)
-    __syncthreads();
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      red[(r0 * C + c0 + e) * 2] = s1[e];
-      red[(r0 * C + c0 + e) * 2 + 1] = s2[b][e];
-    }
-    __syncthreads();
-    bn_write_header(a.acc[b], gridDim.x, 0);
-    double* slot = bn_bwd_slots(a.acc[b], C) + (size_t)blockIdx.x * C * 2;  // this block's own slot
-    for (int c = threadIdx.x; c < C; c += blockDim.x) {
-      float p = 0.f, q = 0.f;
-      for (int k = 0; k < rstep; ++k) {
-        p += red[(k * C + c) * 2];
-        q += red[(k * C + c) * 2 + 1];
-      }
-      slot[2 * c] = (double)p;
-      slot[2 * c + 1] = (double)q;
-    }
+    __syncthreads();          // (the LDS of the other target's sums has been read)
+    block_sums_to_slot(w, a.C, s1, s2[b], a.acc[b]);
   }
 }
 
@@ -1250,7 +1173,7 @@ __global__ __launch_bounds__(256) void bn_eval_bwd_kernel(EvalBwdArgs a) {
 using namespace avt;
 
 // The launches of avt_bn_eval_bwd / avt_bn_eval_bwd_mask: a (mask fields set by the caller) gets the targets and the
-// row dealing of bn_bwd_reduce_launch; the pass, then a finalize per target whose dgamma or dbeta is wanted.
+// reduces' row deal; the pass, then a finalize per target whose dgamma or dbeta is wanted.
 static int bn_eval_bwd_launch(EvalBwdArgs& a, const avt_bn_bwd_target* t1, const avt_bn_bwd_target* t2, long long rows,
                               int C, void* stream, const char* who) {
   AVT_REQUIRE(C % 8 == 0 && C <= 2048 && 256 % (C / 8) == 0, "%s: C=%d unsupported", who, C);
@@ -1271,30 +1194,20 @@ static int bn_eval_bwd_launch(EvalBwdArgs& a, const avt_bn_bwd_target* t1, const
   }
   a.rows = rows;
   a.C = C;
-  long long rpb = (rows + 511) / 512;  // ~2 blocks per CU of rows, as bn_bwd_reduce_launch
-  const int rstep = 256 / (C / 8);
-  rpb = ((rpb + rstep - 1) / rstep) * rstep;
-  if (rpb < rstep) rpb = rstep;
-  a.rows_per_block = (int)rpb;
-  const int nblk = (int)((rows + rpb - 1) / rpb);
+  const RowDeal d = reduce_deal(rows, C);
+  a.rows_per_block = (int)d.rpb;
   hipStream_t st = (hipStream_t)stream;
+  auto launch = [&](auto two, auto bits) {
+    hipLaunchKernelGGL((bn_eval_bwd_kernel<decltype(two)::value, decltype(bits)::value>), dim3(d.nblk), dim3(256), 0, st,
+                       a);
+  };
   if (a.mk) {
-    if (t2)
-      hipLaunchKernelGGL((bn_eval_bwd_kernel<true, true>), dim3(nblk), dim3(256), 0, st, a);
-    else
-      hipLaunchKernelGGL((bn_eval_bwd_kernel<false, true>), dim3(nblk), dim3(256), 0, st, a);
+    if (t2) launch(std::true_type{}, std::true_type{}); else launch(std::false_type{}, std::true_type{});
   } else {
-    if (t2)
-      hipLaunchKernelGGL((bn_eval_bwd_kernel<true, false>), dim3(nblk), dim3(256), 0, st, a);
-    else
-      hipLaunchKernelGGL((bn_eval_bwd_kernel<false, false>), dim3(nblk), dim3(256), 0, st, a);
+    if (t2) launch(std::true_type{}, std::false_type{}); else launch(std::false_type{}, std::false_type{});
   }
-  for (int k = 0; k < (t2 ? 2 : 1); ++k) {
-    if (!a.acc[k]) continue;
-    float* k1 = (float*)(a.acc[k] + kBnHdr);  // (the train-mode rule's means: written, not used here)
-    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + kFinCB - 1) / kFinCB), dim3(kFinThreads), 0, st, a.acc[k], C,
-                       1.0 / (double)rows, ts[k]->dgamma, ts[k]->dbeta, k1, k1 + C);
-  }
+  for (int k = 0; k < (t2 ? 2 : 1); ++k)  // (k1 / k2, the train-mode rule's means: written, not used here)
+    if (a.acc[k]) bn_bwd_finalize_launch(st, C, 1.0 / (double)rows, false, a.acc[k], ts[k]->dgamma, ts[k]->dbeta);
   return check_launch(who);
 }
 
@@ -1411,9 +1324,9 @@ extern "C" int avt_bn_bwd_mask(const void* g, const void* mask, const avt_bn_bwd
   }
   hipStream_t st = (hipStream_t)stream;
   double* acc = (double*)t1->workspace;
-  float* k1 = (float*)(acc + kBnHdr);
+  float* k1 = bn_k1(acc);
   double* acc2 = t2 ? (double*)t2->workspace : nullptr;
-  float* k1b = t2 ? (float*)(acc2 + kBnHdr) : nullptr;
+  float* k1b = t2 ? bn_k1(acc2) : nullptr;
   MaskBwdArgs a{};
   a.g = (const bf16_t*)g;
   a.mk = (const unsigned char*)mask;
@@ -1429,12 +1342,8 @@ extern "C" int avt_bn_bwd_mask(const void* g, const void* mask, const avt_bn_bwd
   }
   a.rows = rows;
   a.C = C;
-  long long rpb = (rows + 511) / 512;  // ~2 blocks per CU of rows, as bn_bwd_reduce_launch
-  const int rstep = 256 / (C / 8);
-  rpb = ((rpb + rstep - 1) / rstep) * rstep;
-  if (rpb < rstep) rpb = rstep;
-  a.rows_per_block = (int)rpb;
-  const int nblk = (int)((rows + rpb - 1) / rpb);
+  const RowDeal d = reduce_deal(rows, C);
+  a.rows_per_block = (int)d.rpb;
   const double inv_rows = 1.0 / (double)rows;
   MaskApplyArgs p{};
   p.g = a.g;
@@ -1449,11 +1358,8 @@ extern "C" int avt_bn_bwd_mask(const void* g, const void* mask, const avt_bn_bwd
   p.nvec = rows * C / 8;
   p.C = C;
   if (t2) {
-    if (!diag_skip(8, st)) hipLaunchKernelGGL(bn_bwd_mask_reduce_kernel<true>, dim3(nblk), dim3(256), 0, st, a);
-    if (diag_skip(64, st)) hipLaunchKernelGGL(bn_bwd_finalize2_kernel, dim3(2 * ((C + kFinCB - 1) / kFinCB)), dim3(kFinThreads), 0, st, acc, acc2, C, inv_rows,
-                       t1->dgamma, t1->dbeta, k1, k1 + C, t2->dgamma, t2->dbeta, k1b, k1b + C);
-    if (!diag_skip(2, st)) hipLaunchKernelGGL(bn_bwd_finalize2_kernel, dim3(2 * ((C + kFinCB - 1) / kFinCB)), dim3(kFinThreads), 0, st, acc, acc2, C, inv_rows,
-                       t1->dgamma, t1->dbeta, k1, k1 + C, t2->dgamma, t2->dbeta, k1b, k1b + C);
+    if (!diag_skip(8, st)) hipLaunchKernelGGL(bn_bwd_mask_reduce_kernel<true>, dim3(d.nblk), dim3(256), 0, st, a);
+    bn_bwd_finalize_launch(st, C, inv_rows, true, acc, t1->dgamma, t1->dbeta, acc2, t2->dgamma, t2->dbeta);
     p.xc2 = (const bf16_t*)t2->xc;
     p.mean2 = t2->mean;
     p.invstd2 = t2->invstd;
@@ -1466,11 +1372,8 @@ extern "C" int avt_bn_bwd_mask(const void* g, const void* mask, const avt_bn_bwd
     else
       hipLaunchKernelGGL(bn_bwd_mask_apply_kernel<true>, dim3(ew_grid(p.nvec)), dim3(256), 0, st, p);
   } else {
-    if (!diag_skip(8, st)) hipLaunchKernelGGL(bn_bwd_mask_reduce_kernel<false>, dim3(nblk), dim3(256), 0, st, a);
-    if (diag_skip(64, st)) hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + kFinCB - 1) / kFinCB), dim3(kFinThreads), 0, st, acc, C, inv_rows, t1->dgamma,
-                       t1->dbeta, k1, k1 + C);
-    if (!diag_skip(2, st)) hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + kFinCB - 1) / kFinCB), dim3(kFinThreads), 0, st, acc, C, inv_rows, t1->dgamma,
-                       t1->dbeta, k1, k1 + C);
+    if (!diag_skip(8, st)) hipLaunchKernelGGL(bn_bwd_mask_reduce_kernel<false>, dim3(d.nblk), dim3(256), 0, st, a);
+    bn_bwd_finalize_launch(st, C, inv_rows, true, acc, t1->dgamma, t1->dbeta);
     if (bn_ew(kEwMaskBwd))
       bn_bwd_mask_apply_rw_launch<false>(p, rows, st);
     else
@@ -1493,16 +1396,13 @@ extern "C" int avt_bn_bwd(const void* g, const void* y, const void* xc, const fl
   AVT_REQUIRE(rows > 0, "bn_bwd: empty input");
   AVT_REQUIRE(((uintptr_t)workspace & 7) == 0, "bn_bwd: workspace must be 8-byte aligned");
   double* acc = (double*)workspace;
-  float* k1 = (float*)(acc + kBnHdr);
+  float* k1 = bn_k1(acc);
   float* k2 = k1 + C;
   hipStream_t st = (hipStream_t)stream;
   if (!diag_skip(8, st))
     bn_bwd_reduce_launch((const bf16_t*)g, (const bf16_t*)y, nullptr, nullptr, (const bf16_t*)xc, mean, invstd, acc,
                          rows, C, st);
-  if (diag_skip(64, st)) hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + kFinCB - 1) / kFinCB), dim3(kFinThreads), 0, st, acc, C, 1.0 / (double)rows,
-                     dgamma, dbeta, k1, k2);
-  if (!diag_skip(2, st)) hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + kFinCB - 1) / kFinCB), dim3(kFinThreads), 0, st, acc, C, 1.0 / (double)rows,
-                     dgamma, dbeta, k1, k2);
+  bn_bwd_finalize_launch(st, C, 1.0 / (double)rows, true, acc, dgamma, dbeta);
   const long long nvec = rows * C / 8;
   if (bn_ew(kEwBwd))
     bn_bwd_apply_rw_launch((const bf16_t*)g, (const bf16_t*)y,
@@ -1526,13 +1426,10 @@ extern "C" int avt_bn_bwd_premasked(const void* gm, const void* xc, const float*
   AVT_REQUIRE(rows > 0, "bn_bwd_premasked: empty input");
   AVT_REQUIRE(((uintptr_t)workspace & 7) == 0, "bn_bwd_premasked: workspace must be 8-byte aligned");
   double* acc = (double*)workspace;
-  float* k1 = (float*)(acc + kBnHdr);
+  float* k1 = bn_k1(acc);
   float* k2 = k1 + C;
   hipStream_t st = (hipStream_t)stream;
-  if (diag_skip(64, st)) hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + kFinCB - 1) / kFinCB), dim3(kFinThreads), 0, st, acc, C, 1.0 / (double)rows,
-                     dgamma, dbeta, k1, k2);
-  if (!diag_skip(2, st)) hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + kFinCB - 1) / kFinCB), dim3(kFinThreads), 0, st, acc, C, 1.0 / (double)rows,
-                     dgamma, dbeta, k1, k2);
+  bn_bwd_finalize_launch(st, C, 1.0 / (double)rows, true, acc, dgamma, dbeta);
   const long long nvec = rows * C / 8;
   if (bn_ew(kEwBwd))
     bn_bwd_apply_rw_launch((const bf16_t*)gm, nullptr,
@@ -1553,15 +1450,12 @@ extern "C" int avt_bn_relu_bwd(const void* g, const void* xc, const float* scale
   AVT_REQUIRE(rows > 0, "bn_relu_bwd: empty input");
   AVT_REQUIRE(((uintptr_t)workspace & 7) == 0, "bn_relu_bwd: workspace must be 8-byte aligned");
   double* acc = (double*)workspace;
-  float* k1 = (float*)(acc + kBnHdr);
+  float* k1 = bn_k1(acc);
   float* k2 = k1 + C;
   hipStream_t st = (hipStream_t)stream;
   if (!diag_skip(8, st))
     bn_bwd_reduce_launch((const bf16_t*)g, nullptr, scale, shift, (const bf16_t*)xc, mean, invstd, acc, rows, C, st);
-  if (diag_skip(64, st)) hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + kFinCB - 1) / kFinCB), dim3(kFinThreads), 0, st, acc, C, 1.0 / (double)rows,
-                     dgamma, dbeta, k1, k2);
-  if (!diag_skip(2, st)) hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + kFinCB - 1) / kFinCB), dim3(kFinThreads), 0, st, acc, C, 1.0 / (double)rows,
-                     dgamma, dbeta, k1, k2);
+  bn_bwd_finalize_launch(st, C, 1.0 / (double)rows, true, acc, dgamma, dbeta);
   const long long nvec = rows * C / 8;
   if (bn_ew(kEwBwd))
     bn_bwd_apply_rw_launch((const bf16_t*)g, nullptr, scale,
@@ -1603,15 +1497,12 @@ extern "C" int avt_stem_maxpool_bn_relu_bwd(const void* gy, const void* idx, con
   AVT_REQUIRE(((uintptr_t)workspace & 7) == 0, "stem_maxpool_bn_relu_bwd: workspace must be 8-byte aligned");
   const int P = (H + 2 - 3) / 2 + 1, Q = (W + 2 - 3) / 2 + 1;
   double* acc = (double*)workspace;
-  float* k1 = (float*)(acc + kBnHdr);
+  float* k1 = bn_k1(acc);
   float* k2 = k1 + C;
   hipStream_t st = (hipStream_t)stream;
   bn_bwd_reduce_launch((const bf16_t*)gy, nullptr, scale, shift, (const bf16_t*)carg, mean, invstd, acc,
                        (long long)N * P * Q, C, st);
-  if (diag_skip(64, st)) hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + kFinCB - 1) / kFinCB), dim3(kFinThreads), 0, st, acc, C,
-                     1.0 / ((double)N * H * W), dgamma, dbeta, k1, k2);
-  if (!diag_skip(2, st)) hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + kFinCB - 1) / kFinCB), dim3(kFinThreads), 0, st, acc, C,
-                     1.0 / ((double)N * H * W), dgamma, dbeta, k1, k2);
+  bn_bwd_finalize_launch(st, C, 1.0 / ((double)N * H * W), true, acc, dgamma, dbeta);
   hipLaunchKernelGGL(stem_maxpool_bn_bwd_apply_kernel<false>, dim3(N * ((H + 1) / 2)), dim3(kStemBwdThreads),
                      (size_t)6 * Q * C, st, (const bf16_t*)gy,
                      (const unsigned char*)idx, (const bf16_t*)c, scale, shift, mean, invstd, gamma, k1, k2,
@@ -1639,11 +1530,10 @@ extern "C" int avt_stem_maxpool_bn_relu_eval_bwd(const void* gy, const void* idx
   hipStream_t st = (hipStream_t)stream;
   if (wants) {
     double* acc = (double*)workspace;
-    float* k1 = (float*)(acc + kBnHdr);  // (the train-mode rule's means: written, not used here)
     bn_bwd_reduce_launch((const bf16_t*)gy, nullptr, scale, shift, (const bf16_t*)carg, mean, invstd, acc,
                          (long long)N * P * Q, C, st);
-    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + kFinCB - 1) / kFinCB), dim3(kFinThreads), 0, st, acc, C,
-                       1.0 / ((double)N * H * W), dgamma, dbeta, k1, k1 + C);
+    // (k1 / k2, the train-mode rule's means: written, not used here)
+    bn_bwd_finalize_launch(st, C, 1.0 / ((double)N * H * W), false, acc, dgamma, dbeta);
   }
   hipLaunchKernelGGL(stem_maxpool_bn_bwd_apply_kernel<true>, dim3(N * ((H + 1) / 2)), dim3(kStemBwdThreads),
                      (size_t)6 * Q * C, st, (const bf16_t*)gy, (const unsigned char*)idx, (const bf16_t*)c, scale, shift,
