@@ -671,10 +671,10 @@ enum { EPI_PLAIN = 0, EPI_BIAS2D = 1, EPI_BIAS3D = 2 };
 
 // BIAS: the bias-epilogue instantiations; VIDB picks their Conv3d / long-tap-list form (avt_conv3d_fwd_bias)
 template <int MODE, int WM, int WN, int TM, int TN, int NST, int BK, bool BIAS = false, bool VIDB = false>
-static void launch_pipe_one(const GemmNTParams& p, const NTPipeArgsV& ta0, hipStream_t st) {
+static bool launch_pipe_one(const GemmNTParams& p, const NTPipeArgsV& ta0, hipStream_t st) {
   constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
   const int grid = ((p.M + BM - 1) / BM) * (p.Ng / BN);
-  if (grid <= 0) return;
+  if (grid <= 0) return true;
   NTPipeArgsV ta = ta0;  // the output grid's row divisors (per parity class for a multi-class dgrad)
   ta.div_hw = make_magic((unsigned)(p.OH * p.OW));
   ta.div_ow = make_magic((unsigned)p.OW);
@@ -690,10 +690,15 @@ static void launch_pipe_one(const GemmNTParams& p, const NTPipeArgsV& ta0, hipSt
   } else if constexpr (BIAS) {  // avt_conv2d_fwd_bias: a 2-D forward of at most 9 taps
     hipLaunchKernelGGL((conv_nt_pipe_kernel<MODE, WM, WN, TM, TN, NST, BK, false, false, true>), dim3(grid),
                        dim3(WM * WN * 64), 0, st, p, narrow_args(ta));
-  } else if (p.IT > 1 || p.OT > 1 || p.KT > 1 || ta.ntaps > 32) {  // Conv3d / the folded 49-tap video stem
+  } else if (p.IT > 1 || p.OT > 1 || p.KT > 1 || ta.ntaps > 9) {
+    // Conv3d, and every 2-D conv of more than 9 taps (5x5, 1x7, the folded 49-tap video stem): the 2-D instantiations
+    // take the 9-tap argument block, and narrow_args() keeps nine taps.  Forward only: the dgrad entry points refuse
+    // a launch of more than 9 taps.
     if constexpr (MODE == MODE_FWD)
       hipLaunchKernelGGL((conv_nt_pipe_kernel<MODE, WM, WN, TM, TN, NST, BK, true>), dim3(grid), dim3(WM * WN * 64), 0,
                          st, p, ta);
+    else
+      return false;  // no long-tap-list dgrad instantiation: the caller reports "no kernel for the plan"
   } else if (MODE == MODE_DGRAD && p.bx != nullptr) {
     hipLaunchKernelGGL((conv_nt_pipe_kernel<MODE, WM, WN, TM, TN, NST, BK, false, true>), dim3(grid),
                        dim3(WM * WN * 64), 0, st, p, narrow_args(ta));
@@ -701,6 +706,7 @@ static void launch_pipe_one(const GemmNTParams& p, const NTPipeArgsV& ta0, hipSt
     hipLaunchKernelGGL((conv_nt_pipe_kernel<MODE, WM, WN, TM, TN, NST, BK>), dim3(grid), dim3(WM * WN * 64), 0, st, p,
                        narrow_args(ta));
   }
+  return true;
 }
 
 // The tap list of a forward or a stride-1 dgrad: all KT*R*S taps in weight order, each displaced by
@@ -721,17 +727,16 @@ static void fill_taps(NTPipeArgsV& ta, const GemmNTParams& p, int mode) {
 
 // Builds the tap list(s) and launches: fwd / stride-1 dgrad in one launch (EPI: on the plain or a bias-epilogue
 // instantiation); a stride-2 dgrad as four parity-class launches, each walking only its class's taps.
-// BK = 64 needs whole 64-channel taps (IC % 64 == 0: plan_nt sees to it).
+// BK = 64 needs whole 64-channel taps (IC % 64 == 0: plan_nt sees to it).  False: a launch had no instantiation.
 template <int MODE, int WM, int WN, int TM, int TN, int NST, int BK, int EPI = EPI_PLAIN>
-static void launch_glds(const GemmNTParams& p, hipStream_t st) {
+static bool launch_glds(const GemmNTParams& p, hipStream_t st) {
   NTPipeArgsV ta{};
   const int batch = p.M / (p.OT * p.OH * p.OW);
   ta.act_bytes = (unsigned)((size_t)batch * p.IT * p.IH * p.IW * p.IC * 2);
   ta.w_bytes = (unsigned)((size_t)p.Ng * p.Kg * 2);
   if (MODE == MODE_FWD || p.stride == 1) {
     fill_taps(ta, p, MODE);
-    launch_pipe_one<MODE, WM, WN, TM, TN, NST, BK, EPI != EPI_PLAIN, EPI == EPI_BIAS3D>(p, ta, st);
-    return;
+    return launch_pipe_one<MODE, WM, WN, TM, TN, NST, BK, EPI != EPI_PLAIN, EPI == EPI_BIAS3D>(p, ta, st);
   }
   ta.cls = 1;
   ta.OHf = p.OH;
@@ -772,7 +777,7 @@ static void launch_glds(const GemmNTParams& p, hipStream_t st) {
       tc.cls_meta[k] = cl[k].n | first << 4 | cl[k].ph << 8 | cl[k].pw << 9;
       start += cl[k].tiles;
     }
-    if (ncl == 0 || start == 0) return;
+    if (ncl == 0 || start == 0) return true;
     tc.ph = cl[0].ph;  // ncls == 1: the plain class mode (then tc.ntaps == cl[0].n)
     tc.pw = cl[0].pw;
     GemmNTParams pc = p;
@@ -780,13 +785,13 @@ static void launch_glds(const GemmNTParams& p, hipStream_t st) {
     pc.OW = (p.OW - cl[0].pw + 1) / 2;
     pc.M = batch * pc.OH * pc.OW;
     if (ncl > 1) pc.M = start / (p.Ng / BN) * BM;  // launch_pipe_one's grid = start; each block takes its class's M
-    launch_pipe_one<MODE, WM, WN, TM, TN, NST, BK>(pc, tc, st);
-    return;
+    return launch_pipe_one<MODE, WM, WN, TM, TN, NST, BK>(pc, tc, st);
   }
   // the class launches that carry the BN-backward epilogue store their partial sums into consecutive
   // slot ranges of one accumulator (conv_epi.h): pass 0 counts the call's slots, pass 1 launches
   constexpr int BMc = WM * TM * 32, BNc = WN * TN * 32;
   int ep_total = 0, ep_base = 0;
+  bool ok = true;
   for (int pass = 0; pass < 2; ++pass)
     for (int ph = 0; ph < 2; ++ph)
       for (int pw = 0; pw < 2; ++pw) {
@@ -820,8 +825,9 @@ static void launch_glds(const GemmNTParams& p, hipStream_t st) {
         pc.bslot_base = ep_base;
         pc.bslot_total = ep_total;
         if (pc.bx != nullptr) ep_base += rtiles;
-        launch_pipe_one<MODE, WM, WN, TM, TN, NST, BK>(pc, tc, st);
+        ok = launch_pipe_one<MODE, WM, WN, TM, TN, NST, BK>(pc, tc, st) && ok;
       }
+  return ok;
 }
 
 constexpr int kHaloPR = 416;  // patch rows the halo kernels' LDS holds: 256 + 2W + 2 <= 416 -> W <= 79
@@ -1206,9 +1212,8 @@ static bool launch_plan(const NtPlan& pl, const GemmNTParams& p, hipStream_t st,
     return true;                                                                            \
   }
 #define AVT_GLDS(WM, WN, TM, TN, NST, BK)                     \
-  if (is(WM, WN, TM, TN, NST, BK)) {                          \
-    launch_glds<MODE, WM, WN, TM, TN, NST, BK, EPI>(p, st);   \
-    return true;                                              \
+  if (is(WM, WN, TM, TN, NST, BK)) {                                \
+    return launch_glds<MODE, WM, WN, TM, TN, NST, BK, EPI>(p, st);  \
   }
   switch (pl.family) {
     case NT_C64:
@@ -1387,6 +1392,8 @@ static int conv2d_fwd_impl(const void* x, const void* wpack, void* y, double* bn
   AVT_REQUIRE(Cp % 32 != 0 || Kg == R * S * Cp, "conv2d_fwd: Kg must equal R*S*C for C%%32==0");
   AVT_REQUIRE(Cp % 32 != 0 || R * S <= kMaxTaps, "conv2d_fwd: at most %d taps for C%%32==0", kMaxTaps);
   AVT_REQUIRE(stride == 1 || stride == 2, "conv2d_fwd: stride must be 1 or 2");
+  AVT_REQUIRE(N >= 1 && H >= 1 && W >= 1 && R >= 1 && S >= 1 && pad >= 0 && H + 2 * pad >= R && W + 2 * pad >= S,
+              "conv2d_fwd: empty input, taps or output, or negative padding");
   GemmNTParams p{};
   AVT_REQUIRE(fwd_params(p, x, wpack, y, N, 1, H, W, Cp, K, 1, R, S, stride, 0, pad, Kg),
               "conv2d_fwd: activation tensors must stay below 2 GiB (32-bit buffer offsets)");
@@ -1457,7 +1464,14 @@ static int conv2d_dgrad_impl(const void* dy, const void* wt, void* dx, const voi
               "conv2d_dgrad: the BatchNorm-backward epilogue needs the LDS-DMA kernels (avt_set_conv_variant(1))");
   AVT_REQUIRE(C % 64 == 0 && K % 32 == 0, "conv2d_dgrad: C=%d K=%d unsupported", C, K);
   AVT_REQUIRE(stride == 1 || stride == 2, "conv2d_dgrad: stride must be 1 or 2");
-  AVT_REQUIRE(R * S <= 32, "conv2d_dgrad: at most 32 taps");
+  AVT_REQUIRE(R >= 1 && S >= 1 && R * S <= 32, "conv2d_dgrad: at most 32 taps");
+  // one launch walks at most 9 taps (the 2-D kernels' argument block): all R*S at stride 1, a parity class's at 2
+  AVT_REQUIRE((stride == 1 ? R * S : ((R + 1) / 2) * ((S + 1) / 2)) <= 9,
+              "conv2d_dgrad: at most 9 taps per launch (R*S at stride 1, ceil(R/2)*ceil(S/2) at stride 2), got %dx%d",
+              R, S);
+  // (a tap list of pad - r, pad - s displacements: the same bound avt_conv3d_dgrad puts on its padding)
+  AVT_REQUIRE(pad >= 0 && pad < R && pad < S, "conv2d_dgrad: padding must be below the kernel size");
+  AVT_REQUIRE(N >= 1 && H >= 1 && W >= 1 && H + 2 * pad >= R && W + 2 * pad >= S, "conv2d_dgrad: empty gradient");
   GemmNTParams p{};
   p.act = (const bf16_t*)dy;
   p.wmat = (const bf16_t*)wt;
@@ -2347,6 +2361,9 @@ static int wgrad_check_shape(const WgShape& s) {
   AVT_REQUIRE(s.Cp % 8 == 0 || s.Cp == 4 || s.Cp == 1, "conv2d_wgrad: C=%d unsupported", s.Cp);
   AVT_REQUIRE(s.Creal <= s.Cp, "conv2d_wgrad: Creal > Cp");
   AVT_REQUIRE(s.Cp % 8 != 0 || s.Creal == s.Cp, "conv2d_wgrad: channel padding only for the stems");
+  AVT_REQUIRE(s.N >= 1 && s.H >= 1 && s.W >= 1 && s.Creal >= 1 && s.K >= 64 && s.R >= 1 && s.S >= 1 && s.pad >= 0 &&
+                  (s.stride == 1 || s.stride == 2) && s.H + 2 * s.pad >= s.R && s.W + 2 * s.pad >= s.S,
+              "conv2d_wgrad: empty input, taps or output, negative padding, or a stride other than 1 and 2");
   return AVT_OK;
 }
 
@@ -2411,10 +2428,7 @@ extern "C" int avt_conv_wgrad_plan(int N, int H, int W, int Cp, int Creal, int K
   AVT_REQUIRE(ws_mode >= 0 && ws_mode <= 3,
               "conv_wgrad_plan: ws_mode=%d (0 no workspace, 1 the workspace, 2 with tickets, 3 with a defer descriptor)", ws_mode);
   const WgShape s{N, H, W, Cp, Creal, K, R, S, stride, pad};
-  if (const int rc = wgrad_check_shape(s)) return rc;
-  AVT_REQUIRE(N >= 1 && H >= 1 && W >= 1 && Cp >= 1 && Creal >= 1 && K >= 64 && R >= 1 && S >= 1 && pad >= 0 &&
-                  (stride == 1 || stride == 2) && H + 2 * pad >= R && W + 2 * pad >= S,
-              "conv_wgrad_plan: empty input, taps or output, negative padding, or a stride other than 1 and 2");
+  if (const int rc = wgrad_check_shape(s)) return rc;  // (the geometry too: what the entry points refuse)
   WgWs ws{0, 0, ws_mode == 3};
   if (ws_mode >= 1) ws.bytes = plan_wgrad(s, kWsAnySlab).slab_bytes;
   if (ws_mode == 2) ws.tickets = plan_wgrad(s, kWsAnyTickets).tickets;

@@ -101,7 +101,9 @@ int avt_copy16(void* dst, const void* src, size_t bytes, int blocks, void* strea
  *
  * y[N,P,Q,K] = conv(x[N,H,W,Cp], wpack[K][Kg]); if bn_acc != NULL the fp32 results' batch-norm
  * statistics are stored into bn_acc (avt_bn_acc_doubles(N*P*Q, K) doubles), for avt_bn_finalize.
- * Cp is 1 or 4 (stems, Kg = R*S*Cp rounded up to 32) or a multiple of 32 (Kg = R*S*Cp). */
+ * Cp is 1 or 4 (stems, Kg = R*S*Cp rounded up to 32) or a multiple of 32 (Kg = R*S*Cp, at most 49 taps); K % 64 == 0;
+ * R, S and pad are independent (any pad >= 0 that leaves an output); stride 1 or 2.  Anything else -- an empty input or
+ * output, a negative pad, tensors of 2 GiB or more -- is refused before any launch (DESIGN 6r has the whole table). */
 size_t avt_bn_acc_doubles(long long rows, int C);
 int avt_conv2d_fwd(const void* x, const void* wpack, void* y, double* bn_acc, int N, int H, int W, int Cp, int K,
                    int R, int S, int stride, int pad, int Kg, void* stream);
@@ -118,7 +120,11 @@ int avt_conv2d_fwd(const void* x, const void* wpack, void* y, double* bn_acc, in
  * avt_stem_bn_relu_maxpool_fwd), more than 9 taps, Kg != R*S*C, strides other than 1 and 2, tensors of 2 GiB or more. */
 int avt_conv2d_fwd_bias(const void* x, const void* wpack, void* y, int N, int H, int W, int Cp, int K, int R, int S,
                         int stride, int pad, int Kg, const float* bias, const void* residual, int relu, void* stream);
-/* dx[N,H,W,C] = dgrad(dy[N,P,Q,K], wt[C][R*S*K]) (+ add[N,H,W,C] if add != NULL; add may alias dx) */
+/* dx[N,H,W,C] = dgrad(dy[N,P,Q,K], wt[C][R*S*K]) (+ add[N,H,W,C] if add != NULL; add may alias dx).  C % 64 == 0,
+ * K % 32 == 0, R and S independent, stride 1 or 2; at most 9 taps per launch -- R*S <= 9 at stride 1, and at stride 2
+ * ceil(R/2)*ceil(S/2) <= 9 with R*S <= 32 (a 5x5 / stride 2 is taken, a 5x5 / stride 1 refused: the 2-D kernels'
+ * argument block holds nine taps); 0 <= pad < min(R, S) (the bound avt_conv3d_dgrad has); a non-empty dy.
+ * So for _mask, _ws and _bn below. */
 int avt_conv2d_dgrad(const void* dy, const void* wt, void* dx, const void* add, int N, int H, int W, int C, int K,
                      int R, int S, int stride, int pad, void* stream);
 /* dx = dgrad(dy, wt) + add * mask: an identity BasicBlock's input gradient (base_models.py:64-67), the
@@ -167,7 +173,9 @@ int avt_conv2d_dgrad_bn(const void* dy, const void* wt, void* dx, const void* ad
                         int R, int S, int stride, int pad, const avt_dgrad_bn_epi* epi, void* stream);
 /* dw[K][R][S][Creal] += wgrad(x[N,H,W,Cp], dy[N,P,Q,K]).  Split-K partials go through an fp32 slab
  * in `workspace` (>= avt_conv2d_wgrad_workspace(...) bytes; deterministic) or, if it is NULL/too
- * small or for the stems, are added with fp32 atomics. */
+ * small or for the stems, are added with fp32 atomics.  K % 64 == 0; Cp % 8 == 0 with Creal == Cp (or the stems' Cp
+ * 4 / 1 with Creal <= Cp); R, S, pad independent, stride 1 or 2; an empty input, output or tap set is refused -- by
+ * every wgrad entry point below and by the two size queries' planner alike. */
 size_t avt_conv2d_wgrad_workspace(int N, int H, int W, int Cp, int Creal, int K, int R, int S, int stride, int pad);
 int avt_conv2d_wgrad(const void* x, const void* dy, float* dw, int N, int H, int W, int Cp, int Creal, int K, int R,
                      int S, int stride, int pad, void* workspace, size_t ws_bytes, void* stream);
@@ -217,7 +225,8 @@ int avt_wgrad_pixtab_register(const void* tab, int N, int H, int W, int Cp, int 
 int avt_conv_stem_dgrad(const void* gy, const float* w, float* gx, int N, int H, int W, int Cin, void* stream);
 
 /* Conv3d, temporal stride 1: y[N,T',P,Q,K] = conv3d(x[N,T,H,W,Cp], wpack[K][(kt,r,s,c)]),
- * T' = T + 2*pad_t - KT + 1, spatial stride 1 or 2; Cp % 32 == 0; KT*R*S <= 27; bn_acc as conv2d_fwd */
+ * T' = T + 2*pad_t - KT + 1, spatial stride 1 or 2; Cp % 32 == 0; K % 64 == 0; KT*R*S <= 49 (KT, R, S, pad_t, pad independent);
+ * bn_acc as conv2d_fwd */
 int avt_conv3d_fwd(const void* x, const void* wpack, void* y, double* bn_acc, int N, int T, int H, int W, int Cp,
                    int K, int KT, int R, int S, int stride, int pad_t, int pad, void* stream);
 /* Inference Conv3d with BatchNorm3d folded in: y = [relu](conv3d(x, wpack) + bias[k] (+ residual)).  Replaces, in eval
@@ -275,7 +284,8 @@ int avt_pack_conv3d_weights_dgrad_batched(const void* descs, int n, int max_bloc
  * gradient of conv3x3x3 (resnet3D.py:14-20; BasicBlock.forward 45-61, `out += residual` :58 entering as `add`).
  * Stride 1 runs avt_conv3d_fwd's kernels (its three-patch halo form included) on dy with pad' = k-1-pad; stride 2
  * walks, per (h%2, w%2) parity class of dx, only the class's spatial taps times the KT temporal taps.  Frames outside
- * a clip contribute zero.  C % 64 == 0, K % 32 == 0. */
+ * a clip contribute zero.  C % 64 == 0, K % 32 == 0, at most 49 taps, pad_t < KT, pad < min(R, S); at stride 1 square
+ * spatial taps only (R == S: one pad' serves both axes of the forward form). */
 int avt_conv3d_dgrad(const void* dy, const void* wt, void* dx, const void* add, int N, int T, int H, int W, int C, int K,
                      int KT, int R, int S, int stride, int pad_t, int pad, void* stream);
 /* dw[K][Cp][KT][R][S] (fp32 OIDHW, the Parameter's layout) += conv3d_weight(x[N,T,H,W,Cp], dy[N,T,P,Q,K]): the weight

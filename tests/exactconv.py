@@ -76,32 +76,46 @@ def mask_from_bits(bits, shape):
 class Case:
     """Operands and lazily computed, cached fp64 references of one conv geometry.
 
-    2-D: case = (N, H, W, C, K, R, stride, pad); activations NHWC, weights OHWI.
-    3-D: case = (N, T, H, W, C, K, stride) (3x3x3, temporal stride 1, pad 1); activations NTHWC, weights OIDHW.
-    px / pw / pdy: the densities of the draws (per case: the 27 x 512 sums may take sparser weights)."""
+    2-D: case = (N, H, W, C, K, R, stride, pad) (square taps) or (N, H, W, C, K, R, S, stride, pad); activations NHWC,
+         weights OHWI.
+    3-D: case = (N, T, H, W, C, K, stride) (3x3x3, pad 1) or (N, T, H, W, C, K, KT, R, S, stride, pad_t, pad), temporal
+         stride 1; activations NTHWC, weights OIDHW.
+    A wgrad-only case (exactconv.DOMAIN_WGRAD) carries the weight gradient's channel count in its C slot (the wgrad
+    entry points take C % 8 == 0, the others C % 32 == 0); Cw is that count.
+    px / pw / pdy: the densities of the draws (per case: the 27 x 512 sums may take sparser weights).
+    The draws are seeded by the case tuple as given: the two short forms keep theirs (tests/golden/exactconv_draws.json)."""
     exact = True
 
     def __init__(self, case, px=0.5, pw=2.0 / 3, pdy=2.0 / 3):
         self.case = tuple(case)
-        self.d3 = len(case) == 7
-        if self.d3:
+        self.d3 = len(case) in (7, 12)
+        if len(case) == 7:
             N, T, H, W, C, K, st = case
-            R, pad = 3, 1
+            KT = R = S = 3
+            pad_t = pad = 1
+        elif len(case) == 12:
+            N, T, H, W, C, K, KT, R, S, st, pad_t, pad = case
+        elif len(case) == 9:
+            N, H, W, C, K, R, S, st, pad = case
+            T, KT, pad_t = 1, 1, 0
         else:
             N, H, W, C, K, R, st, pad = case
-            T = 1
+            T, KT, pad_t, S = 1, 1, 0, R
         self.N, self.T, self.H, self.W, self.C, self.K, self.R, self.st, self.pad = N, T, H, W, C, K, R, st, pad
-        self.P, self.Q = conv_out(H, R, st, pad), conv_out(W, R, st, pad)
+        self.S, self.KT, self.pad_t, self.Cw = S, KT, pad_t, C
+        self.To = T + 2 * pad_t - KT + 1
+        self.P, self.Q = conv_out(H, R, st, pad), conv_out(W, S, st, pad)
+        assert self.To >= 1 and self.P >= 1 and self.Q >= 1, case
         sp_in = (N, T, H, W) if self.d3 else (N, H, W)
-        sp_out = (N, T, self.P, self.Q) if self.d3 else (N, self.P, self.Q)
+        sp_out = (N, self.To, self.P, self.Q) if self.d3 else (N, self.P, self.Q)
         key = self.case
         self.x = acts(sp_in + (C,), px, key, "x")
-        self.w = signs((K, C, 3, 3, 3) if self.d3 else (K, R, R, C), pw, key, "w")
+        self.w = signs((K, C, KT, R, S) if self.d3 else (K, R, S, C), pw, key, "w")
         self.dy = signs(sp_out + (K,), pdy, key, "dy")
         self.add = ints(sp_in + (C,), -3, 3, key, "add")
         self.res = ints(sp_out + (K,), -3, 3, key, "res")
         self.bias = ints((K,), -4, 4, key, "bias")
-        self.xg = ints(sp_in + (C,), 0, 3, key, "xg")
+        self.xg = ints(sp_in + (self.Cw,), 0, 3, key, "xg")
         self.dyg = ints(sp_out + (K,), -3, 3, key, "dyg")
         n_in = self.x.numel()
         self.bits = torch.randint(0, 256, (n_in // 8,), generator=_gen(key, "bits"), dtype=torch.uint8)
@@ -119,7 +133,7 @@ class Case:
 
     def _kw(self):
         if self.d3:
-            return dict(stride=(1, self.st, self.st), padding=1)
+            return dict(stride=(1, self.st, self.st), padding=(self.pad_t, self.pad, self.pad))
         return dict(stride=self.st, padding=self.pad)
 
     def conv(self, x, w, dtype=torch.float64):
@@ -155,7 +169,7 @@ class Case:
     def _terms_in_image(self):
         """(output, term) pairs whose term lies inside the image (padding contributes no term), per (k, c) pair."""
         one = torch.ones(1, 1, *((self.T, self.H, self.W) if self.d3 else (self.H, self.W)))
-        kern = torch.ones(1, 1, *((3, 3, 3) if self.d3 else (self.R, self.R)))
+        kern = torch.ones(1, 1, *((self.KT, self.R, self.S) if self.d3 else (self.R, self.S)))
         f = F.conv3d if self.d3 else F.conv2d
         return float(f(one, kern, **self._kw()).sum()) * self.N
 
@@ -174,7 +188,7 @@ class Case:
         else:
             nz = self.conv_weight((self.xg != 0).float(), (self.dyg != 0).float(), torch.float32).double()
             amax = 9.0
-        pairs = self._terms_in_image() * self.C * self.K
+        pairs = self._terms_in_image() * (self.Cw if kind == "dw" else self.C) * self.K
         fig = dict(max_abs=float(ref.abs().max()), abs_sum=float(nz.max()) * amax, nonzero=float(nz.sum()) / pairs,
                    above255=float((ref.abs() > 255).double().mean()))
         assert fig["abs_sum"] < EXACT, (self.case, kind, fig)
@@ -282,6 +296,155 @@ class Knobs:
 
 def tag(setting):
     return ",".join(f"{n[8:]}={'/'.join(map(str, a))}" for n, *a in setting) or "default"
+
+
+# The knob sweeps of the GPU files.  Forward / dgrad: every knob moved alone from its default, the ring / wave-layout
+# knobs also on the tile they belong to, and with the halo off every tile config of the tap-gather kernel.
+FWD_SWEEP = (
+    [[], [("avt_set_conv_variant", 0)], [("avt_set_halo", 0)], [("avt_set_halo", 2)], [("avt_set_halo8", 0)],
+     [("avt_set_halo8", 1)], [("avt_set_halo8_form", 1)], [("avt_set_halo8_nst", 3)], [("avt_set_halo8_nst", 4)],
+     [("avt_set_halo_tps2", 1)], [("avt_set_c64", 0)], [("avt_set_small_tiles", 0)], [("avt_set_small_tiles", -1)],
+     [("avt_set_stem_kernel", 0)]]
+    + [[("avt_set_halo_stages", a, b)] for a, b in ((2, 2), (3, 3), (4, 4), (5, 5), (2, 4), (2, 5))]
+    + [[("avt_set_halo8", 0), ("avt_set_halo_stages", a, a)] for a in (2, 4, 5)]
+    + [[("avt_set_small_tiles", -1), ("avt_set_halo_stages", a, a)] for a in (2, 5)]
+    + [[("avt_set_halo", 2), k] for k in (("avt_set_halo8_form", 1), ("avt_set_halo8_nst", 4), ("avt_set_halo_tps2", 1),
+                                           ("avt_set_c64", 0))]
+    + [[("avt_set_halo", 0), ("avt_set_nt128_config", c)] for c in range(7)]
+    + [[("avt_set_halo", 0), ("avt_set_nt64_config", c)] for c in range(9)]
+)
+BIAS_SWEEP = [[], [("avt_set_halo", 0)], [("avt_set_halo", 2)], [("avt_set_halo8", 0)], [("avt_set_halo8", 1)],
+              [("avt_set_c64", 0)], [("avt_set_small_tiles", 0)], [("avt_set_small_tiles", -1)],
+              [("avt_set_halo", 0), ("avt_set_small_tiles", -1)], [("avt_set_halo", 2), ("avt_set_c64", 0)]]
+DGRAD_SWEEP = FWD_SWEEP + [[("avt_set_s2_dgrad_one", 0)], [("avt_set_s2_dgrad_one", 1)],
+                           [("avt_set_s2_dgrad_one", 0), ("avt_set_small_tiles", -1)]]
+# Conv3d: avt_set_halo3d 0/1/2, the two-taps-per-barrier knob, and the tile configs the Conv3d planner picks from
+# (test_conv3d_tile_configs: nt64 0/1/2, nt128 1/6) on the tap-gather form
+SWEEP_3D = ([[], [("avt_set_halo3d", 0)], [("avt_set_halo3d", 1)], [("avt_set_halo3d", 2)], [("avt_set_halo_tps2", 0)],
+             [("avt_set_halo_tps2", 1)], [("avt_set_halo3d", 2), ("avt_set_halo_tps2", 1)]]
+            + [[("avt_set_halo3d", 0), ("avt_set_nt64_config", v)] for v in (0, 1, 2)]
+            + [[("avt_set_halo3d", 0), ("avt_set_nt128_config", v)] for v in (1, 6)])
+MANY = ("avt_set_wgrad_policy", 1 << 20, 1)  # more blocks asked for than there are k-tiles: every split one k-tile (or pair)
+GATHER = ("avt_set_wgrad_halo", 0)
+WGRAD_SWEEP = (
+    [("ws", []), ("ws", [("avt_set_wgrad_tiles", 0)]), ("ws", [("avt_set_wgrad_tiles", 1)])]
+    + [("ws", [("avt_set_wgrad_halo", h)]) for h in (0, 1, 2, 3)]
+    + [("ws", [("avt_set_wgrad_halo", 2), ("avt_set_wgrad_row3", kg, -1, pf)]) for kg in (1, 2, 4) for pf in (0, 1)]
+    + [("ws", [GATHER, ("avt_set_wgrad_nst", a, b)]) for a, b in ((4, 3), (6, 4), (8, 5))]
+    + [("ws", [("avt_set_stem_wgrad", 0)]), ("ws", [("avt_set_stem_wgrad", 1)])]
+    + [("ws", [GATHER, ("avt_set_wgrad_pixtab", 0)]), ("pixtab", [GATHER, ("avt_set_wgrad_pixtab", 1)]),
+       ("pixtab", [GATHER, ("avt_set_wgrad_pixtab", 1), MANY])]
+    + [("split4", [GATHER, MANY]), ("split4", [GATHER, MANY, ("avt_set_wgrad_tiles", 0)])]
+    + [("ws", [("avt_set_wgrad_slots_pct", 65)]), ("ws", [("avt_set_wgrad_slots_pct", 100)])]
+    + [("null", []), ("null", [GATHER]), ("null", [GATHER, MANY]), ("null", [("avt_set_stem_wgrad", 0)])]
+    + [("atomic", [GATHER, MANY, ("avt_set_wgrad_slab_max", 2, 16)])]
+    + [("tk", [("avt_set_wgrad_fused", 1, -1), ("avt_set_wgrad_slots_pct", 100)]),
+       ("tk", [GATHER, ("avt_set_wgrad_fused", 1, -1), ("avt_set_wgrad_policy", 0, 2)])]
+    + [("defer", [("avt_set_wgrad_slots_pct", 100)]), ("defer", [GATHER, ("avt_set_wgrad_policy", 0, 2)])]
+)
+FWD_PLAN_INTS, WGRAD_PLAN_INTS = 10, 24
+
+
+def fwd_plan(c, cp, epi, dgrad=False):
+    """avt_conv_fwd_plan (a host query: no device) under the knobs as they stand; a stride-1 dgrad is the forward of dy
+    with C and K swapped and pad' = taps - 1 - pad.  The query takes one pad: for R != S it is asked with R's, so the
+    tuple is exact for square taps only (the callers that deduplicate settings by it run every setting at R != S)."""
+    import ctypes
+
+    from avt_amd._lib import call
+
+    out = (ctypes.c_int * FWD_PLAN_INTS)()
+    if dgrad:
+        call("avt_conv_fwd_plan", c.N, c.To, c.P, c.Q, c.K, c.C, c.KT, c.R, c.S, 1, c.KT - 1 - c.pad_t, c.R - 1 - c.pad,
+             epi, out)
+    else:
+        call("avt_conv_fwd_plan", c.N, c.T, c.H, c.W, cp, c.K, c.KT, c.R, c.S, c.st, c.pad_t, c.pad, epi, out)
+    return tuple(out)
+
+
+def fwd_plans(c, cp, sweep, epi, dgrad=False):
+    """[(plan, setting)] of the settings whose plan tuple differs from every earlier one (host queries only)."""
+    seen, out = set(), []
+    for setting in sweep:
+        with Knobs(setting):
+            plan = fwd_plan(c, cp, epi, dgrad)
+        if plan not in seen:
+            seen.add(plan)
+            out.append((plan, setting))
+    return out
+
+
+def wgrad_plan(c, cp, ws_mode):
+    """avt_conv_wgrad_plan (a host query) of a 2-D case under the knobs as they stand."""
+    import ctypes
+
+    from avt_amd._lib import call
+
+    out = (ctypes.c_int * WGRAD_PLAN_INTS)()
+    call("avt_conv_wgrad_plan", c.N, c.H, c.W, cp, c.Cw, c.K, c.R, c.S, c.st, c.pad, ws_mode, out)
+    return tuple(out)
+
+
+def nan_tensor(*shape, dtype=torch.bfloat16):
+    return torch.full(shape, float("nan"), device="cuda", dtype=dtype)
+
+
+def run_wgrad(c, o, mode, what):
+    """One 2-D wgrad under the knobs as they stand, into dw pre-filled with 0.25; returns ([dw, ...], info) (defer:
+    two).  o: the device operands (cp, xg, dyg)."""
+    import ctypes
+
+    from avt_amd._lib import SlabReduceDesc, call, query
+
+    cp = o["cp"]
+    g = (c.N, c.H, c.W, cp, c.Cw, c.K, c.R, c.S, c.st, c.pad)
+    wsb = int(query("avt_conv2d_wgrad_workspace", *g))  # after the knobs: the plan sizes it
+    ws = nan_tensor(max(wsb // 4, 4), dtype=torch.float32)    # any contents
+    dw = torch.full((c.K, c.R, c.S, c.Cw), PREFILL, device="cuda")
+    npix = c.N * c.P * c.Q
+    if mode == "split4" and npix >= 8 * 32:
+        assert wsb >= 4 * c.K * c.R * c.S * c.Cw * 4, (what, wsb)  # at least 4 splits through the slab
+    if mode == "atomic" and npix >= 8 * 32:
+        assert wsb == 0, (what, wsb)  # beyond avt_set_wgrad_slab_max's splits the plan has no slab: fp32 atomics
+    if mode in ("ws", "split4", "atomic"):
+        call("avt_conv2d_wgrad", P(o["xg"]), P(o["dyg"]), P(dw), *g, P(ws), wsb, S())
+    elif mode == "null":
+        call("avt_conv2d_wgrad", P(o["xg"]), P(o["dyg"]), P(dw), *g, None, 0, S())
+    elif mode == "pixtab":
+        geo = (c.N, c.H, c.W, cp, c.R, c.S, c.st, c.pad)
+        nb = int(query("avt_wgrad_pixtab_bytes", c.N, c.H, c.W, c.R, c.S, c.st, c.pad))
+        assert nb > 0, what
+        tab = torch.full((nb // 4,), -1, device="cuda", dtype=torch.int32)
+        call("avt_wgrad_pixtab_build", P(tab), *geo, S())
+        torch.cuda.synchronize()
+        try:
+            call("avt_wgrad_pixtab_register", P(tab), *geo)
+            call("avt_conv2d_wgrad", P(o["xg"]), P(o["dyg"]), P(dw), *g, P(ws), wsb, S())
+            torch.cuda.synchronize()
+        finally:
+            call("avt_wgrad_pixtab_register", None, *geo)
+    elif mode == "tk":
+        nt = int(query("avt_conv2d_wgrad_tickets", *g))
+        tk = torch.zeros(max(nt, 1), device="cuda", dtype=torch.int32)
+        call("avt_conv2d_wgrad_tk", P(o["xg"]), P(o["dyg"]), P(dw), *g, P(ws), wsb, P(tk) if nt else None, nt, S())
+        torch.cuda.synchronize()
+        assert int(tk.abs().sum()) == 0, what + ": tickets not left zero"
+        return [dw], f"{nt} tickets"
+    else:  # defer: two slabs, one avt_wgrad_reduce_batch launch
+        dws, descs = [dw, dw.clone()], []
+        for d in dws:
+            w2 = nan_tensor(max(wsb // 4, 4), dtype=torch.float32)
+            desc = SlabReduceDesc()
+            call("avt_conv2d_wgrad_defer", P(o["xg"]), P(o["dyg"]), P(d), *g, P(w2), wsb, ctypes.byref(desc), S())
+            if desc.splits > 0:
+                descs.append(desc)
+        if descs:
+            arr = (SlabReduceDesc * len(descs))(*descs)
+            call("avt_wgrad_reduce_batch", arr, len(descs), S())
+        torch.cuda.synchronize()
+        return dws, f"{len(descs)} slabs batched"
+    torch.cuda.synchronize()
+    return [dw], f"{wsb} slab bytes"
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -497,3 +660,149 @@ def get_video_stem(shape):
     if tuple(shape) not in _STEMS:
         _STEMS[tuple(shape)] = VideoStem(shape)
     return _STEMS[tuple(shape)]
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The accepted domain of include/avt.h off the ResNet-18 grid (test_conv_domain_cpu.py, test_conv_domain_gpu.py,
+# test_conv3d_domain_gpu.py).  The smallest shapes at which each path exists -- N <= 3, H, W <= 13,
+# T <= 5 -- with odd and even sizes, M off the multiples of 64, P*Q < 32; the knob sweeps force the big tiles at
+# small M.  Sized on the CPU by test_exactconv_cpu.py: every case passes figures()'s conditions at the default densities
+# (the shapes are small: 9 x 1024 and 45 x 192 terms stay below the 1 % above-255 cap), so none carries its own.
+# ---------------------------------------------------------------------------------------------------------------------
+# forward, bias epilogue (at most 9 taps: more is a documented refusal of avt_conv2d_fwd_bias), split-K
+# (N, H, W, C, K, R, S, stride, pad)
+DOMAIN_2D = [
+    (2, 9, 11, 32, 64, 3, 3, 1, 1),      # C % 64 == 32: the k32 fallback; M = 198
+    (1, 5, 6, 96, 192, 3, 3, 1, 1),      # P*Q = 30; Ng = 192
+    (2, 8, 8, 160, 320, 1, 1, 1, 0),     # M = 128
+    (3, 7, 9, 192, 384, 1, 3, 1, 1),     # R != S; pad > (R-1)/2 along h
+    (2, 10, 7, 320, 64, 3, 1, 2, 1),     # R != S at stride 2; pad > (S-1)/2 along w
+    (2, 12, 13, 96, 64, 2, 2, 2, 0),     # even taps
+    (1, 9, 9, 32, 192, 5, 5, 1, 2),      # 25 taps
+    (2, 6, 13, 32, 64, 1, 7, 1, 0),
+    (1, 11, 12, 32, 64, 7, 7, 2, 3),     # 49 taps at C = 32: the long tap list
+    (2, 6, 5, 192, 192, 3, 3, 1, 0),     # pad 0 under 3x3
+    (2, 6, 7, 64, 320, 3, 3, 1, 2),      # pad 2 > (R-1)/2
+    (3, 13, 13, 192, 128, 3, 3, 1, 1),   # the halo forms on 3 chunks of 64 channels (split-K: 3 | 3)
+    (2, 7, 7, 320, 384, 3, 3, 1, 1),     # the halo forms on 5 chunks, 3 column tiles (split-K: 5 | 5)
+    (2, 8, 8, 1024, 64, 1, 1, 1, 0),
+    (1, 7, 7, 2048, 192, 1, 1, 2, 0),
+    (2, 4, 4, 32, 2048, 1, 1, 1, 0),
+    (1, 5, 5, 160, 1024, 1, 1, 1, 0),
+    (1, 3, 3, 2048, 2048, 1, 1, 1, 0),
+    (1, 4, 4, 1024, 1024, 3, 3, 1, 1),   # P*Q = 16: 9 x 1024 terms
+    # the Bottleneck trio, each at stride 1 and 2
+    (2, 8, 9, 256, 64, 1, 1, 1, 0), (2, 8, 9, 256, 64, 1, 1, 2, 0),
+    (2, 8, 9, 64, 64, 3, 3, 1, 1), (2, 8, 9, 64, 64, 3, 3, 2, 1),
+    (2, 8, 9, 64, 256, 1, 1, 1, 0), (2, 8, 9, 64, 256, 1, 1, 2, 0),
+]
+# dgrad: plain, add, in place, mask, the three BN epilogues, _ws.  C % 64 == 0, K % 32 == 0, at most 32 taps
+DOMAIN_DGRAD = [
+    (2, 9, 11, 64, 32, 3, 3, 1, 1),
+    (1, 5, 6, 192, 96, 3, 3, 1, 1),      # P*Q = 30; Ng = 192; IC % 64 == 32
+    (2, 8, 7, 320, 160, 1, 1, 1, 0),
+    (2, 7, 9, 192, 192, 1, 3, 1, 0),     # R != S at stride 1 (pad < min(R, S): pad 0)
+    (2, 8, 9, 64, 160, 2, 3, 1, 1),      # R != S with a pad on both axes
+    (2, 10, 7, 64, 96, 3, 2, 2, 1),      # stride 2, R != S: the parity classes' tap counts differ per axis
+    (2, 9, 8, 192, 160, 1, 3, 2, 0),     # stride 2, R != S, pad 0: classes without a tap
+    (2, 12, 13, 64, 32, 2, 2, 2, 0),
+    (1, 6, 6, 1024, 192, 1, 1, 1, 0),
+    (2, 4, 4, 64, 2048, 1, 1, 1, 0),
+    (2, 9, 10, 64, 32, 5, 5, 2, 2),      # 25 taps at stride 2: parity classes of 9, 6, 6 and 4 taps
+    (2, 6, 7, 192, 96, 3, 3, 2, 1),
+    (2, 6, 5, 320, 32, 3, 3, 1, 0),      # pad 0 under 3x3
+    (3, 13, 13, 128, 192, 3, 3, 1, 1),   # the halo forms of the dgrad (and its split-K) on 3 chunks
+]
+# wgrad: every form of test_wgrad_every_form.  The tuple's C slot is Cw, the weight gradient's channel count
+DOMAIN_WGRAD = [
+    (2, 9, 11, 8, 64, 1, 1, 1, 0),       # 8 columns: ncols < 64
+    (2, 9, 11, 8, 64, 3, 3, 1, 1),       # 72 columns
+    (3, 7, 9, 16, 192, 1, 3, 1, 1),      # 48 columns
+    (2, 8, 8, 24, 64, 3, 3, 1, 1),       # 216 columns: % 128 != 0, > 128
+    (2, 13, 12, 24, 320, 3, 3, 2, 1),
+    (1, 5, 6, 40, 192, 5, 5, 1, 2),      # 1000 columns; P*Q = 30
+    (3, 13, 13, 40, 64, 3, 3, 1, 1),     # 507 pixels: splits
+    (2, 10, 7, 96, 320, 1, 1, 2, 0),
+    (3, 12, 13, 96, 192, 3, 3, 1, 1),    # 468 pixels: splits
+    (2, 6, 6, 160, 64, 1, 3, 1, 0),
+    (2, 7, 7, 160, 320, 3, 3, 1, 0),
+    (2, 9, 8, 192, 192, 3, 3, 1, 1),     # C % 64 == 0: the halo arms' shape test at K = 192
+    (1, 4, 5, 192, 64, 5, 5, 2, 2),
+]
+SPLIT_WGRAD = [(3, 13, 13, 40, 64, 3, 3, 1, 1), (3, 12, 13, 96, 192, 3, 3, 1, 1)]  # >= 2 splits from the workspace size
+# (N, T, H, W, C, K, KT, R, S, stride, pad_t, pad): avt_conv3d_fwd / _fwd_bias, and avt_conv3d_wgrad where the padding is
+# temporal 'same' (wgrad3d_ok); the dgrad has its own list (C % 64 == 0, K % 32 == 0, square taps at stride 1)
+DOMAIN_3D = [
+    (2, 3, 6, 5, 32, 64, 3, 3, 3, 1, 1, 1),
+    (1, 4, 7, 6, 96, 192, 3, 3, 3, 1, 1, 1),    # 27 x 96 terms; Ng = 192
+    (1, 3, 5, 6, 192, 64, 3, 3, 3, 2, 1, 1),
+    (1, 3, 6, 7, 192, 64, 3, 3, 3, 1, 1, 1),     # the three-patch halo form on 3 chunks of 64 channels, 256 x 64 tile
+    (2, 3, 6, 7, 192, 128, 3, 3, 3, 1, 1, 1),    # ... and its 256 x 128 tile
+    (2, 5, 6, 7, 32, 192, 3, 3, 3, 1, 0, 1),    # pad_t 0: T' = 3
+    (2, 3, 7, 6, 96, 64, 3, 3, 3, 1, 2, 0),     # pad_t 2 > (KT-1)/2: T' = 5; spatial pad 0
+    (2, 4, 8, 7, 96, 64, 1, 3, 3, 1, 0, 1),
+    (1, 5, 6, 6, 32, 192, 3, 1, 1, 1, 1, 0),
+    (2, 3, 9, 8, 192, 64, 1, 1, 1, 2, 0, 0),
+    (2, 4, 6, 7, 96, 192, 2, 2, 2, 1, 0, 0),
+    (2, 4, 6, 7, 32, 64, 2, 2, 2, 2, 1, 1),
+    (1, 5, 6, 5, 32, 64, 5, 3, 3, 1, 2, 1),     # 45 taps: the long tap list
+    (1, 4, 5, 6, 192, 192, 5, 3, 3, 2, 2, 1),   # 45 x 192 terms
+    (2, 3, 5, 7, 64, 128, 1, 3, 1, 2, 0, 1),    # R != S (no stride-1 dgrad: square taps only)
+]
+DOMAIN_3D_DGRAD = [  # C in {64, 192}, K in {32, 96}
+    (2, 3, 6, 5, 64, 32, 3, 3, 3, 1, 1, 1),
+    (1, 4, 7, 6, 192, 96, 3, 3, 3, 1, 1, 1),
+    (1, 3, 5, 6, 192, 32, 3, 3, 3, 2, 1, 1),
+    (1, 3, 6, 7, 64, 192, 3, 3, 3, 1, 1, 1),     # the forward form of this dgrad is the three-patch kernel: IC = 192
+    (2, 3, 6, 7, 128, 192, 3, 3, 3, 1, 1, 1),    # ... on its 256 x 128 tile
+    (2, 5, 6, 7, 64, 96, 3, 3, 3, 1, 0, 1),     # pad_t 0
+    (2, 3, 7, 6, 64, 96, 3, 3, 3, 1, 2, 0),     # pad_t 2, spatial pad 0
+    (2, 4, 8, 7, 192, 32, 1, 3, 3, 1, 0, 1),
+    (1, 5, 6, 6, 64, 96, 3, 1, 1, 1, 1, 0),
+    (2, 3, 9, 8, 192, 96, 1, 1, 1, 2, 0, 0),    # three of the four classes without a tap
+    (2, 4, 6, 7, 64, 32, 2, 2, 2, 1, 0, 0),
+    (2, 4, 6, 7, 64, 96, 2, 2, 2, 2, 1, 1),
+    (1, 5, 6, 5, 64, 32, 5, 3, 3, 1, 2, 1),     # 45 taps
+    (2, 3, 5, 7, 64, 96, 1, 3, 1, 2, 0, 0),     # R != S at stride 2
+]
+
+
+def wgrad3d_ok(case):
+    """avt_conv3d_wgrad's documented domain within DOMAIN_3D: temporal 'same' padding."""
+    N, T, H, W, C, K, KT, R, S, st, pad_t, pad = case
+    return 2 * pad_t == KT - 1
+
+
+# One step across each documented edge: (entry point, case, why).  The case tuples are complete geometries (nothing is
+# drawn for them: the GPU files pass pre-filled buffers of the right sizes and expect them back untouched).
+OUTSIDE = [
+    ("avt_conv2d_fwd", (2, 6, 6, 48, 64, 3, 3, 1, 1), "C = 48: a multiple of 8, not of 32"),
+    ("avt_conv2d_fwd", (2, 6, 6, 32, 96, 3, 3, 1, 1), "K = 96"),
+    ("avt_conv2d_fwd", (2, 6, 6, 32, 32, 3, 3, 1, 1), "K = 32"),
+    ("avt_conv2d_fwd", (1, 12, 12, 32, 64, 5, 10, 1, 2), "50 taps"),
+    ("avt_conv2d_fwd", (2, 9, 9, 32, 64, 3, 3, 3, 1), "stride 3"),
+    ("avt_conv2d_fwd_bias", (2, 6, 6, 48, 64, 3, 3, 1, 1), "C = 48"),
+    ("avt_conv2d_fwd_bias", (2, 6, 6, 32, 96, 3, 3, 1, 1), "K = 96"),
+    ("avt_conv2d_fwd_bias", (2, 8, 8, 32, 64, 2, 5, 1, 0), "10 taps: the bias epilogue's narrow form ends at 9"),
+    ("avt_conv2d_fwd_bias", (2, 6, 6, 32, 64, 3, 3, 1, 1), "an aliasing residual"),
+    ("avt_conv2d_dgrad", (2, 6, 6, 32, 64, 3, 3, 1, 1), "C = 32"),
+    ("avt_conv2d_dgrad", (2, 6, 6, 64, 48, 3, 3, 1, 1), "K = 48"),
+    ("avt_conv2d_dgrad", (2, 6, 6, 64, 32, 3, 3, 1, 3), "pad >= R"),
+    ("avt_conv2d_dgrad", (2, 9, 9, 64, 32, 3, 3, 3, 1), "stride 3"),
+    ("avt_conv2d_dgrad", (1, 12, 12, 64, 32, 3, 11, 1, 1), "33 taps"),
+    ("avt_conv2d_dgrad", (1, 9, 9, 64, 32, 5, 5, 1, 2), "25 taps in one launch: the 2-D argument block holds 9"),
+    ("avt_conv2d_dgrad_mask", (2, 6, 6, 64, 32, 3, 3, 1, 1), "add aliasing dx"),
+    ("avt_conv2d_wgrad", (2, 6, 6, 12, 64, 3, 3, 1, 1), "C = 12"),
+    ("avt_conv2d_wgrad", (2, 6, 6, 16, 96, 3, 3, 1, 1), "K = 96"),
+    ("avt_conv2d_wgrad", (2, 9, 9, 16, 64, 3, 3, 3, 1), "stride 3"),
+    ("avt_conv3d_fwd", (1, 3, 6, 6, 48, 64, 3, 3, 3, 1, 1, 1), "C = 48"),
+    ("avt_conv3d_fwd", (1, 3, 6, 6, 32, 96, 3, 3, 3, 1, 1, 1), "K = 96"),
+    ("avt_conv3d_fwd", (1, 5, 12, 6, 32, 64, 5, 10, 1, 1, 2, 0), "50 taps"),
+    ("avt_conv3d_fwd", (1, 3, 9, 9, 32, 64, 3, 3, 3, 3, 1, 1), "stride 3"),
+    ("avt_conv3d_fwd_bias", (1, 3, 6, 6, 32, 64, 3, 3, 3, 1, 1, 1), "an aliasing residual"),
+    ("avt_conv3d_dgrad", (1, 3, 6, 6, 32, 64, 3, 3, 3, 1, 1, 1), "C = 32"),
+    ("avt_conv3d_dgrad", (1, 3, 6, 6, 64, 32, 3, 3, 3, 1, 1, 3), "pad >= R"),
+    ("avt_conv3d_dgrad", (1, 3, 6, 6, 64, 32, 3, 3, 1, 1, 1, 0), "R != S at stride 1: square spatial taps only"),
+    ("avt_conv3d_wgrad", (1, 3, 6, 6, 32, 64, 3, 3, 3, 1, 0, 1), "pad_t 0 under KT 3: not temporal 'same' padding"),
+    ("avt_conv3d_wgrad", (1, 3, 6, 6, 24, 64, 3, 3, 3, 1, 1, 1), "C = 24"),
+]

@@ -25,12 +25,7 @@ def _keep_alive():
     ec.KEEP.clear()
 
 
-# avt_set_halo3d 0/1/2, the two-taps-per-barrier knob, and the tile configs the Conv3d planner picks from
-# (test_conv3d_tile_configs: nt64 0/1/2, nt128 1/6) on the tap-gather form
-SWEEP = ([[], [("avt_set_halo3d", 0)], [("avt_set_halo3d", 1)], [("avt_set_halo3d", 2)], [("avt_set_halo_tps2", 0)],
-          [("avt_set_halo_tps2", 1)], [("avt_set_halo3d", 2), ("avt_set_halo_tps2", 1)]]
-         + [[("avt_set_halo3d", 0), ("avt_set_nt64_config", v)] for v in (0, 1, 2)]
-         + [[("avt_set_halo3d", 0), ("avt_set_nt128_config", v)] for v in (1, 6)])
+SWEEP = ec.SWEEP_3D  # shared with test_conv3d_domain_gpu.py
 CASES = ec.cases_3d()
 SPLIT_CASES = CASES[7:9]
 _OPS = {}
@@ -45,10 +40,14 @@ def _ops(case):
     if case not in _OPS:
         c = ec.get_case(case)
         w = c.w.to(DEV)
-        wp = torch.empty(c.K, 27 * c.C, device=DEV, dtype=torch.bfloat16)
-        wt = torch.empty(c.C, 27 * c.K, device=DEV, dtype=torch.bfloat16)
-        call("avt_pack_conv3d_weight", P(w), P(wp), c.K, c.C, 3, 3, 3, 0, S())
-        call("avt_pack_conv3d_weight_dgrad", P(w), P(wt), c.K, c.C, 3, 3, 3, S())
+        taps = c.KT * c.R * c.S
+        wp = torch.empty(c.K, taps * c.C, device=DEV, dtype=torch.bfloat16)
+        wt = torch.empty(c.C, taps * c.K, device=DEV, dtype=torch.bfloat16)
+        call("avt_pack_conv3d_weight", P(w), P(wp), c.K, c.C, c.KT, c.R, c.S, 0, S())
+        if c.K % 64 == 0:
+            call("avt_pack_conv3d_weight_dgrad", P(w), P(wt), c.K, c.C, c.KT, c.R, c.S, S())
+        else:  # the pack kernel takes K % 64 == 0, avt_conv3d_dgrad K % 32 == 0: the same layout by hand (include/avt.h)
+            wt = w.flip(2, 3, 4).permute(1, 2, 3, 4, 0).reshape(c.C, taps * c.K).to(torch.bfloat16).contiguous()
         torch.cuda.synchronize()
         bf = lambda t: t.to(torch.bfloat16).to(DEV)
         _OPS[case] = dict(wp=wp, wt=wt, x=bf(c.x), xg=bf(c.xg), dy=bf(c.dy), dyg=bf(c.dyg), add=bf(c.add),
@@ -57,29 +56,18 @@ def _ops(case):
 
 
 def _geo(c):
-    return (c.N, c.T, c.H, c.W, c.C, c.K, 3, 3, 3, c.st, 1, 1)
+    return (c.N, c.T, c.H, c.W, c.C, c.K, c.KT, c.R, c.S, c.st, c.pad_t, c.pad)
 
 
 def _plans(case, epi, dgrad=False):
     """[(plan, setting)] of SWEEP's settings with distinct avt_conv_fwd_plan tuples (T and KT set; a stride-1 dgrad is
     the forward of dy with C and K swapped)."""
     c = ec.get_case(case)
-    seen, out = set(), []
-    for setting in SWEEP:
-        buf = (ctypes.c_int * 10)()
-        with Knobs(setting):
-            if dgrad:
-                call("avt_conv_fwd_plan", c.N, c.T, c.P, c.Q, c.K, c.C, 3, 3, 3, 1, 1, 1, epi, buf)
-            else:
-                call("avt_conv_fwd_plan", *_geo(c), epi, buf)
-        if tuple(buf) not in seen:
-            seen.add(tuple(buf))
-            out.append((tuple(buf), setting))
-    return out
+    return ec.fwd_plans(c, c.C, SWEEP, epi, dgrad)
 
 
 @pytest.mark.parametrize("case", CASES, ids=str)
-def test_conv3d_fwd_every_plan(case):
+def test_conv3d_fwd_every_plan(case, record=True):
     """avt_conv3d_fwd with its BN accumulator under every distinct plan of the sweep, and avt_conv3d_fwd_bias with a
     residual and ReLU (the fp32 bias joins the accumulator before the first rounding, residual and ReLU the rounded
     value: DESIGN 6l)."""
@@ -90,26 +78,28 @@ def test_conv3d_fwd_every_plan(case):
     plans = _plans(case, 0)
     for plan, setting in plans:
         with Knobs(setting):
-            y = _nan(c.N, c.T, c.P, c.Q, c.K)
-            acc = _nan(int(query("avt_bn_acc_doubles", c.N * c.T * c.P * c.Q, c.K)), dtype=torch.float64)
+            y = _nan(c.N, c.To, c.P, c.Q, c.K)
+            acc = _nan(int(query("avt_bn_acc_doubles", c.N * c.To * c.P * c.Q, c.K)), dtype=torch.float64)
             call("avt_conv3d_fwd", P(o["x"]), P(o["wp"]), P(y), P(acc), *_geo(c), S())
             torch.cuda.synchronize()
             what = f"conv3d_fwd {case} [{_tag(setting)}] plan {plan}"
             ec.assert_bf16(y, ref, what)
             ec.assert_fwd_acc(acc, ref, what)
-    _RAN[case] = {p[0] for p, _ in plans}
+    fams = {p[0] for p, _ in plans}
+    if record:  # (test_conv3d_domain_gpu.py runs this body on its own cases)
+        _RAN[case] = fams
     v = ec.bf16_rne(ref + c.bias.double())
     want = {False: v, True: ec.bf16_rne(v + c.res.double()).clamp_min(0)}
     bplans = _plans(case, 2)
     for plan, setting in bplans:
         with Knobs(setting):
             for full in (False, True):
-                y = _nan(c.N, c.T, c.P, c.Q, c.K)
+                y = _nan(c.N, c.To, c.P, c.Q, c.K)
                 call("avt_conv3d_fwd_bias", P(o["x"]), P(o["wp"]), P(y), *_geo(c), P(o["bias"]),
                      P(o["res"]) if full else None, int(full), S())
                 torch.cuda.synchronize()
                 ec.assert_rounded(y, want[full], f"conv3d_fwd_bias {case} [{_tag(setting)}] plan {plan} res+relu={full}")
-    print(f"conv3d fwd {case}: {len(plans)} + {len(bplans)} (bias) distinct plans, families {sorted(_RAN[case])}, "
+    print(f"conv3d fwd {case}: {len(plans)} + {len(bplans)} (bias) distinct plans, families {sorted(fams)}, "
           f"above 255: {fig['above255']:.2e}")
 
 
@@ -156,11 +146,11 @@ def test_conv3d_wgrad_exact(case):
     o = _ops(case)
     wsb = int(query("avt_conv3d_wgrad_workspace", *_geo(c)))
     assert wsb > 0
-    Ng = (27 * c.C + 127) // 128 * 128  # slab bytes = splits * K * Ng * 4
+    Ng = (c.KT * c.R * c.S * c.C + 127) // 128 * 128  # slab bytes = splits * K * Ng * 4
     if case in SPLIT_CASES:
         assert wsb % (c.K * Ng * 4) == 0 and wsb // (c.K * Ng * 4) >= 2, (wsb, c.K, Ng)
     ws = _nan(wsb // 4, dtype=torch.float32)  # any contents
-    dw = torch.full((c.K, c.C, 3, 3, 3), ec.PREFILL, device=DEV)
+    dw = torch.full((c.K, c.C, c.KT, c.R, c.S), ec.PREFILL, device=DEV)
     rc = lib().avt_conv3d_wgrad(P(o["xg"]), P(o["dyg"]), P(dw), *_geo(c), P(ws), wsb, S())
     assert rc == 0, lib().avt_last_error()
     torch.cuda.synchronize()

@@ -3,10 +3,16 @@
   * every case of test_conv_exact_gpu.py and test_conv3d_exact_gpu.py passes the conditions under which its sums are
     exact in any order (this test sizes the draws);
   * the fp32 and the fp64 CPU references are equal -- the order-independence claim, checked once;
-  * sensitivity: ten faults, injected one at a time into a torch emulation of the conv (operands or index maps
+  * the off-grid cases of the domain files (exactconv.DOMAIN_*) pass the same conditions, and the generalised Case
+    leaves the old cases' draws as they were (tests/golden/exactconv_draws.json);
+  * sensitivity: fifteen faults, injected one at a time into a torch emulation of the conv (operands or index maps
     edited, no kernel), are each flagged by the equality comparator.  For the record the test prints whether the
     per-kernel files' old criterion (max|got - ref| / max|ref| < 8e-3, 2e-4 for a weight gradient) would have caught
     the same fault on its own kind of operands, a randn draw of the same shape; that is not asserted."""
+import json
+import os
+import zlib
+
 import pytest
 import torch
 import torch.nn.functional as F
@@ -31,6 +37,66 @@ def test_conditions_and_order_independence(case):
     if len(case) == 8 and case[3] == case[4] == 64 and case[5] == 3:
         # the layer-1 kernel's bias epilogue rounds once, the others twice: both must be the identity
         assert c.figures("y")["one_rounding_safe"], case
+
+
+def test_old_cases_keep_their_draws():
+    """The generalised Case leaves the draws of the two short tuple forms as they were: the CRC-32 of the operands'
+    bytes for one strided, one c64 and two 3-D cases, recorded from the commit before the generalisation."""
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "exactconv_draws.json")) as f:
+        golden = json.load(f)
+    assert len(golden) == 4
+    for key, digests in golden.items():
+        case = tuple(int(v) for v in key.strip("()").split(","))
+        assert case in ec.STRIDED_CASES + ec.C64_CASES + ec.cases_3d(), case
+        c = ec.Case(case)
+        assert set(digests) == {"x", "w", "dy", "xg", "dyg"}
+        for name, crc in digests.items():
+            assert zlib.crc32(getattr(c, name).contiguous().numpy().tobytes()) == crc, (case, name)
+
+
+DOMAIN = ([(c, ("y",)) for c in ec.DOMAIN_2D] + [(c, ("dx",)) for c in ec.DOMAIN_DGRAD]
+          + [(c, ("dw",)) for c in ec.DOMAIN_WGRAD]
+          + [(c, ("y", "dw") if ec.wgrad3d_ok(c) else ("y",)) for c in ec.DOMAIN_3D]
+          + [(c, ("dx",)) for c in ec.DOMAIN_3D_DGRAD])
+
+
+@pytest.mark.parametrize("case,kinds", DOMAIN, ids=lambda v: str(v) if isinstance(v, tuple) and len(v) > 3 else "")
+def test_domain_conditions(case, kinds):
+    """The same conditions, unrelaxed, for every off-grid case of the domain files and the kinds they compare; the
+    shapes keep N <= 3, H, W <= 13, T <= 5."""
+    c = ec.get_case(case)
+    assert c.N <= 3 and c.H <= 13 and c.W <= 13 and c.T <= 5, case
+    for kind in kinds:
+        _show(case, kind, c.figures(kind))
+        r64, r32 = c.ref(kind), c.ref(kind, torch.float32)
+        assert torch.equal(r32.double(), r64), (case, kind)
+    if "y" in kinds and not c.d3 and c.R * c.S <= 9:
+        assert c.figures("y")["one_rounding_safe"], case  # whichever kernel takes the bias epilogue
+
+
+def test_domain_lists_cover_the_issue():
+    """The sweeps the lists promise: channel counts, tap shapes, pads, strides, the Bottleneck trio, M off the
+    multiples of 64 and P*Q < 32."""
+    f = [ec.get_case(c) for c in ec.DOMAIN_2D]
+    assert {c.C for c in f} >= {32, 96, 160, 192, 320, 1024, 2048} and {c.K for c in f} >= {64, 192, 320, 384, 1024, 2048}
+    assert {(c.R, c.S) for c in f} >= {(1, 1), (1, 3), (3, 1), (2, 2), (3, 3), (5, 5), (1, 7), (7, 7)}
+    assert {c.pad for c in f} >= {0, 1, 2} and {c.st for c in f} == {1, 2}
+    assert all(c.R * c.S == 1 or c.P * c.Q <= 16 for c in f if max(c.C, c.K) >= 1024)
+    for st in (1, 2):
+        assert {(c.C, c.K, c.R) for c in f if c.st == st} >= {(256, 64, 1), (64, 64, 3), (64, 256, 1)}
+    assert any((c.N * c.P * c.Q) % 64 for c in f) and any(c.P * c.Q < 32 for c in f)
+    d = [ec.get_case(c) for c in ec.DOMAIN_DGRAD]
+    assert {c.C for c in d} >= {64, 192, 320, 1024} and {c.K for c in d} >= {32, 96, 160, 192, 2048}
+    assert any(c.R != c.S and c.st == 2 for c in d) and any(c.R != c.S and c.st == 1 for c in d)
+    w = [ec.get_case(c) for c in ec.DOMAIN_WGRAD]
+    assert {c.Cw for c in w} >= {8, 16, 24, 40, 96, 160, 192} and {c.K for c in w} >= {64, 192, 320}
+    assert {(c.R, c.S) for c in w} >= {(1, 1), (3, 3), (1, 3), (5, 5)} and len(ec.SPLIT_WGRAD) >= 2
+    v = [ec.get_case(c) for c in ec.DOMAIN_3D]
+    assert {(c.KT, c.R, c.S) for c in v} >= {(3, 3, 3), (1, 3, 3), (3, 1, 1), (1, 1, 1), (2, 2, 2), (5, 3, 3)}
+    assert {c.pad_t for c in v} >= {0, 1, 2} and {c.C for c in v} >= {32, 96, 192} and {c.K for c in v} >= {64, 192}
+    assert any((c.KT, c.R, c.S, c.st) == (1, 1, 1, 2) for c in v)
+    g = [ec.get_case(c) for c in ec.DOMAIN_3D_DGRAD]
+    assert {c.C for c in g} >= {64, 192} and {c.K for c in g} >= {32, 96, 192}
 
 
 @pytest.mark.parametrize("shape", ec.VIDEO_STEM_SHAPES, ids=str)
@@ -177,7 +243,68 @@ def _fault_stem_pad_channel(c):
     return y.permute(0, 2, 3, 1).contiguous(), c.ref("y"), False
 
 
+# faults only a shape off the ResNet-18 grid can show, on the cases of the domain files
+C96 = (1, 5, 6, 96, 192, 3, 3, 1, 1)
+R1S3 = (3, 7, 9, 192, 384, 1, 3, 1, 1)
+COLS216 = (2, 8, 8, 24, 64, 3, 3, 1, 1)
+PADT2 = (2, 3, 7, 6, 96, 64, 3, 3, 3, 1, 2, 0)
+
+
+def _fault_last_32_channels_dropped(c):
+    assert c.C % 64 == 32
+    x = c.x.clone()
+    x[..., c.C - 32:] = 0  # a 64-deep k-tile walked over C // 64 whole chunks only
+    return c.conv(x, c.w), c.ref("y"), False
+
+
+def _shifted_taps(c, swap):
+    """A stride-1 2-D forward as a sum over taps of the input displaced by (r - pad, s - pad), zero outside the image;
+    swap: the displacement built as (s - pad, r - pad)."""
+    m = max(c.R, c.S) + c.pad
+    xp = F.pad(c.x.double(), (0, 0, m, m, m, m))
+    y = torch.zeros(c.N, c.P, c.Q, c.K, dtype=torch.float64)
+    for r in range(c.R):
+        for s in range(c.S):
+            dy, dx = (s - c.pad, r - c.pad) if swap else (r - c.pad, s - c.pad)
+            y += xp[:, m + dy:m + dy + c.P, m + dx:m + dx + c.Q, :] @ c.w[:, r, s, :].double().T
+    return y
+
+
+def _fault_r_s_swapped_in_displacement(c):
+    assert c.R != c.S and c.st == 1
+    if c.exact:
+        assert torch.equal(_shifted_taps(c, False), c.ref("y"))  # the emulation is the conv
+    return _shifted_taps(c, True), c.ref("y"), False
+
+
+def _fault_wgrad_tail_columns_zeroed(c):
+    ncols = c.R * c.S * c.Cw
+    assert ncols % 128 and ncols > 128
+    dw = c.ref("dw").clone().reshape(c.K, ncols)
+    dw[:, ncols // 128 * 128:] = 0  # the partial last 128-column tile never stored
+    return dw.reshape(c.ref("dw").shape), c.ref("dw"), True
+
+
+def _fault_pad_t_applied_as_pad(c):
+    assert c.d3 and c.pad_t != c.pad
+    xp = F.pad(c.x.double(), (0, 0, 0, 0, 0, 0, c.pad, 2 * c.pad_t - c.pad))  # frames displaced by kt - pad
+    y = c._cl(F.conv3d(c._cf(xp), c.w.double(), stride=(1, c.st, c.st), padding=(0, c.pad, c.pad)))
+    return y, c.ref("y"), False
+
+
+def _fault_k192_last_tile_from_previous(c):
+    assert c.K == 192
+    y = c.ref("y").clone()
+    y[..., 128:] = y[..., 64:128]  # the third 64-wide column tile addressed as the second
+    return y, c.ref("y"), False
+
+
 FAULTS = {
+    "the last 32 channels of every tap dropped at C % 64 == 32": (_fault_last_32_channels_dropped, C96),
+    "R and S swapped in the tap displacement": (_fault_r_s_swapped_in_displacement, R1S3),
+    "the wgrad columns past the last full 128 zeroed": (_fault_wgrad_tail_columns_zeroed, COLS216),
+    "pad_t applied as pad": (_fault_pad_t_applied_as_pad, PADT2),
+    "the last 64 output channels of a K = 192 conv taken from the tile before": (_fault_k192_last_tile_from_previous, C96),
     "one 8-channel chunk of one tap dropped in a 128-row tile's last row": (_fault_chunk_dropped, BIG),
     "taps (r, s) and (s, r) swapped for one output channel": (_fault_taps_swapped, MID),
     "right halo column at w = W-1 reads the next row's first pixel": (_fault_halo_wraps, MID),
