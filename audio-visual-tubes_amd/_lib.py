@@ -16,7 +16,7 @@ CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_PATH = os.path.join(PKG_DIR, "libavt.so")
 # A/B measurement only: load another in-tree build of the same ABI (e.g. libavt_base.so)
 LOAD_PATH = os.environ.get("AVT_LIB_PATH", LIB_PATH)
-SOURCES = ["conv_gemm.hip", "bn.hip", "pool.hip", "head.hip", "misc.hip", "tube.hip", "conv3d_bwd.hip", "eval.hip", "audio.hip", "frames.hip", "render.hip", "cls.hip"]
+SOURCES = ["conv_gemm.hip", "bn.hip", "pool.hip", "head.hip", "misc.hip", "tube.hip", "conv3d_bwd.hip", "eval.hip", "audio.hip", "frames.hip", "render.hip", "cls.hip", "flow.hip"]
 
 _P = ctypes.c_void_p
 _I = ctypes.c_int
@@ -162,6 +162,11 @@ SIGNATURES = {
     "avt_pair_ciou": (_I, [_P, _I, _I, _P, _P]),
     "avt_heatmap_upsample": (_I, [_P, _I, _I, _I, _I, _I, _P, _P]),
     "avt_render_overlay": (_I, [_P, _I, _I, _I, _P, _F, _D, _P, _F, _D, _F, _P, _P, _P]),
+    "avt_flow_workspace_bytes": (_Z, [_I, _L]),
+    "avt_flow_warp": (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _I, _P, _P]),
+    "avt_flow_consistency": (_I, [_P, _I, _I, _P, _I, _P, _P, _P]),
+    "avt_flow_loss": (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P]),
+    "avt_flow_color": (_I, [_P, _I, _I, _I, _P, _P, _P, _P]),
     "avt_spectrogram_segments": (_I, [_L, _I]),
     "avt_spectrogram": (_I, [_P, _I, _L, _I, _F, _P, _P]),
     "avt_frames_transform": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _P]),

@@ -173,7 +173,7 @@ def tube_indices(T: int, sampling_rate: int) -> list:
 
 
 @torch.no_grad()
-def evaluate_tube(model, videos, sampling_rate: int = 16, render_to=None) -> dict:
+def evaluate_tube(model, videos, sampling_rate: int = 16, render_to=None, flow_fn=None) -> dict:
     """The per-video test loop of tube training (train_3D.py:146-186; flow.py:170-210 for AVENet).  ``videos`` yields
     (frames [1,3,T,H,W], spec [1,1,F,Tt], gt [n,224,224]) with one gt map per sampled frame, or (name, frames, spec,
     gt).  Per video: one eval-mode forward of ``frames[:, :, tube_indices(T, sampling_rate)]`` with the one
@@ -182,7 +182,11 @@ def evaluate_tube(model, videos, sampling_rate: int = 16, render_to=None) -> dic
     consecutive predictions.  Returns ``dict(ciou=, auc=, mtc=, per_video=[dict(name=, ciou=, auc=, mtc=, cious=)])``,
     the three headline numbers the means over the videos.  A video with fewer than two sampled frames has no mTC:
     ValueError.  ``render_to(name, images)``, when given, receives ``render.overlay(sampled frames, pred=maps, gt=gt)``
-    ([n,H,W,3] uint8 on the device) per video; it needs frames of the gt maps' size.
+    ([n,H,W,3] uint8 on the device) per video; it needs frames of the gt maps' size.  ``flow_fn(name, sampled frames
+    [1,3,n,H,W])``, when given, returns the optical flow between the consecutive sampled frames as a field [n-1,S,S,2]
+    in pixels of the prediction maps (S = 224); each per-video dict then gains ``mtc_flow``, the flow-compensated mTC
+    (``flow.mtc_flow``: frame i's prediction warped onto frame i+1 before the cIoU), and the result its mean over the
+    videos.  Without it the result is what it was.
 
     The reference's tube loop resizes ``heatmap[step][0, 0]`` -- one row of the step-th map (train_3D.py:157-158).
     This is the per-frame protocol every other loop of the reference runs: the whole map of each sampled frame."""
@@ -212,6 +216,10 @@ def evaluate_tube(model, videos, sampling_rate: int = 16, render_to=None) -> dic
             cious = stats[:, 0].tolist()
             per_video.append(dict(name=name, ciou=float(np.mean(np.array(cious) >= 0.5)), auc=auc_from_cious(cious),
                                   mtc=mtc(maps), cious=cious))
+            if flow_fn is not None:
+                from . import flow
+
+                per_video[-1]["mtc_flow"] = flow.mtc_flow(maps, flow_fn(name, sampled), "pixels")
             if render_to is not None:
                 from . import render
 
@@ -220,6 +228,7 @@ def evaluate_tube(model, videos, sampling_rate: int = 16, render_to=None) -> dic
         model.train(was_training)
     if not per_video:
         raise ValueError("avt: evaluate_tube got no video")
-    out = {k: float(np.sum([v[k] for v in per_video]) / len(per_video)) for k in ("ciou", "auc", "mtc")}
+    keys = ("ciou", "auc", "mtc") + (("mtc_flow",) if flow_fn is not None else ())
+    out = {k: float(np.sum([v[k] for v in per_video]) / len(per_video)) for k in keys}
     out["per_video"] = per_video
     return out

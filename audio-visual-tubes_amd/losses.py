@@ -7,6 +7,9 @@ forward launch and scaled by the upstream gradient in backward.
   mean over (clip, frame pair) of |sum_hw heatmap[:, s+1] - sum_hw heatmap[:, s]|.
 * ``FlipLoss()(heatmap, flipped_heatmap)`` (losses.py:25-36): nn.L1Loss()(flipped_heatmap,
   RandomHorizontalFlip(p=1)(heatmap)), the flip along the last dimension.
+* ``FlowLoss()(heatmap, field)`` (flow.py:117 ``criterion2 = FlowLoss(14 * 14)``; losses.py of the reference never
+  defines it), heatmap [b, t, h, w], field [b, t-1, h, w, 2]: PropagationLoss under flow compensation, the mean over
+  (clip, frame pair, pixel) of |warp(heatmap[:, s], field[:, s]) - heatmap[:, s+1]| (``flow.warp``'s bilinear warp).
 
 Each runs on a multi-block grid (no size limit): gradients elementwise, the loss as per-block partial
 sums that one block adds in a fixed order (deterministic, run to run).
@@ -121,3 +124,51 @@ class FlipLoss(nn.Module):
 
     def forward(self, heatmap: torch.Tensor, flipped_heatmap: torch.Tensor) -> torch.Tensor:
         return _FlipLossFn.apply(heatmap, flipped_heatmap)
+
+
+class _FlowLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, heatmap: torch.Tensor, field: torch.Tensor, coords: int):
+        if not heatmap.is_cuda or not field.is_cuda:
+            raise RuntimeError("avt: FlowLoss runs on the GPU (no CPU path)")
+        if heatmap.dim() != 4:
+            raise ValueError(f"avt: FlowLoss expects a heatmap [b, t, h, w], got {tuple(heatmap.shape)}")
+        b, t, h, w = heatmap.shape
+        if t < 2:
+            raise ValueError("avt: FlowLoss needs t >= 2 (there is no frame pair to compare)")
+        if b < 1 or h * w < 1 or h * w > 1024:
+            raise ValueError(f"avt: FlowLoss takes b >= 1 maps of 1 <= h*w <= 1024 pixels, got {tuple(heatmap.shape)}")
+        if tuple(field.shape) != (b, t - 1, h, w, 2):
+            raise ValueError(f"avt: FlowLoss expects a field [{b}, {t - 1}, {h}, {w}, 2], got {tuple(field.shape)}")
+        if field.requires_grad:
+            raise ValueError("avt: FlowLoss gives the field no gradient (the flow estimator is frozen, flow.py:107); "
+                             "pass field.detach()")
+        x = heatmap.detach().contiguous().float()
+        f = field.contiguous().float()
+        loss = torch.empty((), device=x.device, dtype=torch.float32)
+        dx = torch.empty_like(x) if heatmap.requires_grad else None
+        call("avt_flow_loss", P(x), b, t, h, w, P(f), coords, P(loss), P(dx), P(_workspace(x, b * t)), stream_ptr())
+        ctx.save_for_backward(dx)
+        ctx.in_dtype = heatmap.dtype
+        return loss.to(heatmap.dtype)
+
+    @staticmethod
+    def backward(ctx, g):
+        (dx,) = ctx.saved_tensors
+        return (dx * g).to(ctx.in_dtype), None, None
+
+
+class FlowLoss(nn.Module):
+    """The ``FlowLoss`` flow.py:117 constructs.  ``coords`` as in ``flow.warp`` ("pixels": displacements in pixels of
+    the heat map; "grid": grid_sample coordinates).  The reference's one positional argument (``FlowLoss(14 * 14)``,
+    the number of pixels) is accepted and not used: the maps carry their own size."""
+
+    def __init__(self, n_pixels=None, *, coords: str = "pixels"):
+        super().__init__()
+        from .flow import coords_id
+
+        self.coords = coords
+        self._coords_id = coords_id(coords)
+
+    def forward(self, heatmap: torch.Tensor, field: torch.Tensor) -> torch.Tensor:
+        return _FlowLossFn.apply(heatmap, field, self._coords_id)

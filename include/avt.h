@@ -532,6 +532,77 @@ int avt_render_overlay(const float* img, int N, int H, int W, const float* map0,
                        const float* map1, float scale1, double w1, float wimg, const unsigned char* lut,
                        unsigned char* out, void* stream);
 
+/* ---- flow-compensated temporal consistency (flow.py:133-157; utils.flow2img, utils.py:64-192) ----
+ * Everything downstream of "an optical-flow field exists"; the estimator (FlowNet2) is not part of this library.
+ *
+ * bilinear_at(m [H][W], ix, iy), the one sampling definition of the three entries below: x0 = floor(ix), y0 =
+ * floor(iy); nw = (x0+1-ix)*(y0+1-iy), ne = (ix-x0)*(y0+1-iy), sw = (x0+1-ix)*(iy-y0), se = (ix-x0)*(iy-y0); result
+ * nw*m[y0][x0] + ne*m[y0][x0+1] + sw*m[y0+1][x0] + se*m[y0+1][x0+1], the terms added in that order starting from the
+ * first neighbour inside [0,W) x [0,H); a neighbour outside contributes nothing (zero padding), none inside gives +0,
+ * and so does a NaN or infinite ix or iy.  Every difference, product and sum is one separately rounded fp32
+ * operation (no FMA).  A finite position of any magnitude is safe (it is clamped before the int conversion).
+ *
+ * coords selects what a field entry (f0, f1) of output pixel (x, y) means; channel 0 is horizontal:
+ *   0 "grid":   grid_sample coordinates, ix = ((f0 + 1) * W - 1) / 2, iy = ((f1 + 1) * H - 1) / 2 (torch's
+ *               un-normalisation for align_corners=False, four fp32 operations each).  The output has the field's
+ *               own size [Ho][Wo], which may differ from [H][W].  This is flow.py:152 to the letter: the reference
+ *               hands FlowNet2's PIXEL displacements to grid_sample as if they were normalised coordinates, so its
+ *               own warp samples far outside the map almost everywhere.
+ *   1 "pixels": displacements in pixels of the map, ix = x + f0, iy = y + f1 (one fp32 add each); the output has
+ *               the map's size.  This is what the metric flow.py:143 cites means.
+ * Every field pointer must be 8-byte aligned (both components of an entry are one load); a pointer that is only
+ * 4-byte aligned is refused.  All entries: sizes >= 1 and H*W, Ho*Wo <= 2^30; an unknown coords, a NULL pointer or a
+ * bad size is refused with AVT_EINVAL before any launch, the outputs untouched.  No float atomics: the same inputs
+ * give the same bytes. */
+/* bytes of the scratch avt_flow_consistency (maps = T - 1, pixels = S*S) and avt_flow_color (maps = N, pixels = H*W)
+ * take: per-chunk counts / maxima of their first launch.  Any contents; 8-byte aligned. */
+size_t avt_flow_workspace_bytes(int maps, long long pixels);
+/* grid_sample(src, field, mode='bilinear', padding_mode='zeros', align_corners=False) (flow.py:152) or its pixel-
+ * displacement form: out[n][y][x] = bilinear_at(src[n], position of (x, y) from field[n][y][x]).  src [N][H][W] fp32
+ * (src_u8 = 0) or u8 (src_u8 = 1: a non-zero byte is 1, as avt_pair_ciou reads its maps); field [N][Ho][Wo][2] fp32;
+ * out [N][Ho][Wo] fp32.  coords = 1 needs Ho = H and Wo = W. */
+int avt_flow_warp(const void* src, int src_u8, int N, int H, int W, const float* field, int Ho, int Wo, int coords,
+                  float* out, void* stream);
+/* The flow-compensated avt_pair_ciou: pred [T][S][S] u8 binary maps (avt_localize_ciou's pred_out), field
+ * [T-1][S][S][2] fp32; out [T-1][3] fp64 = (cIoU, intersection, denominator) of utils.Evaluator.cal_CIOU(warped,
+ * pred[k+1], 0.5) (utils.py:209-214): infer = bilinear_at(pred[k]) >= 0.5, gt = pred[k+1], inter = sum infer*gt, denom
+ * = sum gt + sum infer*(gt == 0), cIoU = inter / denom (0 / 0 = NaN, as avt_pair_ciou gives).  The warped map is
+ * never stored; the sums are integer counts (exact), converted to fp64 for the divide.  With a zero field in pixel
+ * coordinates out[k][0] is avt_pair_ciou's out[k] bit for bit.  2 <= T <= 65536, 1 <= S <= 32768. */
+int avt_flow_consistency(const void* pred, int T, int S, const float* field, int coords, double* out, void* workspace,
+                         void* stream);
+/* The trainable counterpart at heat-map resolution (the FlowLoss flow.py:117 constructs and losses.py never defines):
+ * x [b][t][h][w] fp32, field [b][t-1][h][w][2] fp32; with d_s(p) = bilinear_at(x[c][s])(p) - x[c][s+1][p] and
+ * k = 1 / (float(b) * float(t-1) * float(h*w)),
+ *   *loss = k * sum |d_s(p)|: one partial per (clip, pair) into ws (a thread's p = tid, tid + 256, ... in order, then
+ *           the 64 lanes of a wave by xor butterfly 32 .. 1, then the 4 waves in order), the partials summed by one
+ *           block the same way;
+ *   dx (optional) [b][t][h][w]: dx[c][s][q] = (+0 + k * G) - k * sign(d_{s-1}(q)), where G = sum over output pixels p
+ *           increasing, corners nw, ne, sw, se, of sign(d_s(p)) * weight(p, corner) for the corners that are q -- the
+ *           first bracket for s < t-1 only, the last term for s > 0 only; sign(0) = 0 (torch's abs backward); each
+ *           operation rounded separately.  A gather, not a scatter: one block per (clip, frame) keeps the pair's signs,
+ *           weights and cell indices in LDS.
+ * The field gets no gradient (flow.py:159 backpropagates the hard-way loss alone; the estimator is frozen,
+ * flow.py:107).  ws: b*(t-1) floats.  t >= 2; h*w <= 1024 (the model's maps are 14 x 14 and 16 x 16), above it
+ * refused. */
+int avt_flow_loss(const float* x, int b, int t, int h, int w, const float* field, int coords, float* loss, float* dx,
+                  float* ws, void* stream);
+/* utils.flow2img (utils.py:155-192) of N fields: field [N][H][W][2] fp32 -> out [N][H][W][3] u8 (RGB).  The field is
+ * not modified (the reference overwrites its argument).  Per field in fp64, each operation rounded separately as
+ * numpy evaluates it: a component with |.| > 1e7 marks the pixel unknown and both are zeroed; maxrad = max(-1, max
+ * sqrt(u^2 + v^2)); u = u / maxrad + 2^-52, likewise v; then compute_color (utils.py:112-154): a NaN u or v zeroes
+ * both and flags the pixel; rad = sqrt(u^2 + v^2), a = atan2(-v, -u) / pi, fk = (a + 1) / 2 * 54 + 1, k0 = floor(fk),
+ * k1 = k0 + 1 (56 wraps to 1), f = fk - k0; per channel col = (1 - f) * wheel[k0-1] / 255 + f * wheel[k1-1] / 255,
+ * col = 1 - rad * (1 - col) where rad <= 1, else col * 0.75; byte = u8(floor(255 * col * (1 - flag))); unknown pixels
+ * 0.  wheel [55][3] u8: the Middlebury colour wheel (utils.py:64-111).  An all-zero field has maxrad = 0, every
+ * pixel NaN, and comes out black, as in the reference.  One thing is ours: a NaN input does not take part in the
+ * maximum (numpy's max would return NaN, Python's max(-1, nan) then -1, and every other pixel of the field would be
+ * drawn negated); here the rest of the field is drawn as if that pixel were zero.  The device's fp64 sqrt and atan2
+ * need not round as the host's do: a byte may differ by 1 where 255 * col lies within rounding of an integer.
+ * workspace: avt_flow_workspace_bytes(N, H*W).  1 <= N <= 65535. */
+int avt_flow_color(const float* field, int N, int H, int W, const unsigned char* wheel, unsigned char* out,
+                   void* workspace, void* stream);
+
 /* ---- audio front end (datasets/dataloader.py:86-96): waveform -> normalised log-spectrogram ---- */
 /* segments of a length-N waveform at hop = nperseg - noverlap (the reference: 512 - 1) */
 int avt_spectrogram_segments(long long n_samples, int hop);
